@@ -126,9 +126,23 @@ def parse(argv=None):
                     help="hang guard: a step whose heartbeat has not landed after this many "
                          "seconds (or a host that stops issuing steps) ends the rank with exit "
                          "code 3 and a diagnostic on stderr; 0 disables it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step left behind as "
+                         "DIR/<name>.npy (float32 / float64): its logits, the dense parameters, "
+                         "embedding rows (those the step updated and a fixed seeded sample) and "
+                         "the mean loss of the timed steps. The same arguments give the same "
+                         "inputs from run to run, so two builds compare output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements. A plain run sets up, warms up, "
+                         "times --steps steps and prints the result line; the headline bench "
+                         "has no secondary measurement of its own (CPU / eager baselines, other "
+                         "models, emulated ranks and profiles are separate scripts or options), "
+                         "so today this changes nothing")
     args = ap.parse_args(argv)
     if args.host_data:
         args.data = "host"
+    if args.dump_outputs and args.emulate_world > 1:
+        ap.error("--dump-outputs is for the measured job itself, not --emulate-world")
     return args
 
 
@@ -305,6 +319,57 @@ def measure(args, info, cfg, world: int, group, rank: int) -> dict:
             "loss": loss, "setup_s": setup_s, "comm": comm,
             "modelled_us": step_stats[1] if step_stats is not None else 0.0,
             "rw_grows_timed": (tr.emb.rw_grows if tr.emb.rw_tables else 0) - grows0}
+
+
+DUMP_ROWS_PER_TABLE = 128
+
+
+def dump_outputs(dirpath: str, tr, cfg, loss: float, world: int) -> dict:
+    """--dump-outputs: what the last timed step left on this rank, as
+    ``dirpath/<name>.npy`` (float32, the loss float64; ~15 MB for the default
+    model). The tables are far larger than the 64 MB budget, so of each table
+    held here two fixed sets of rows are written: the rows the last batch's
+    first ``DUMP_ROWS_PER_TABLE`` ids looked up (the step updated them; one
+    GPU only, where the static id buffer still holds that batch) and a seeded
+    sample of rows (mostly untouched: checks the initialisation and that the
+    update wrote nowhere else). Returns name -> shape."""
+    import numpy as np
+
+    tr.sync_streams()
+    torch.cuda.synchronize()
+    os.makedirs(dirpath, exist_ok=True)
+    out = {"logits": tr.logits.float(), "dense_params": tr.fp.p.float(),
+           "train_loss": torch.tensor([loss], dtype=torch.float64)}
+    n = DUMP_ROWS_PER_TABLE
+    B, pool = tr.B, cfg.pooling_factors()
+    g = torch.Generator(device="cpu")
+    g.manual_seed(1234)
+    touched, sampled, off = [], [], 0
+    for t, L in enumerate(pool):
+        held = tr.emb.get_table_weight(t)
+        seg = tr.ids[off: off + B * L] if world == 1 else None
+        off += B * L
+        pick = torch.randint(0, 1 << 62, (n,), generator=g)       # drawn for every table
+        if held is None or held[1].shape[0] == 0:
+            continue
+        rows = held[1]
+        sampled.append(rows[(pick % rows.shape[0]).to(rows.device)].float().cpu())
+        if seg is not None:
+            ids = seg[:n]
+            if ids.numel() < n:                                    # batch smaller than n bags
+                ids = torch.cat([ids, ids.new_zeros(n - ids.numel())])
+            touched.append(rows[ids.clamp(0, rows.shape[0] - 1)].float().cpu())
+    if sampled:
+        out["emb_rows_sampled"] = torch.stack(sampled)
+    if touched:
+        out["emb_rows_updated"] = torch.stack(touched)
+    shapes = {}
+    for name, v in out.items():
+        a = np.ascontiguousarray(v.detach().cpu().numpy())
+        assert a.dtype in (np.float32, np.float64)
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
 
 
 def _graph_name(tr):
@@ -485,6 +550,10 @@ def main(argv=None):
         reset()
         sys.exit(4)
     if info.rank == 0:
+        if args.dump_outputs:
+            shapes = dump_outputs(args.dump_outputs, tr, cfg, r["loss"], world)
+            print(json.dumps({"dump_outputs": args.dump_outputs, "arrays": shapes}),
+                  file=sys.stderr, flush=True)
         print(json.dumps({"plan": tr.plan.summary(), "setup_s": round(r["setup_s"], 1),
                           "train_loss": round(r["loss"], 4), "graph": _graph_name(tr),
                           "host_issue_us_per_step": round((r["host_s"] - r["wait_s"])

@@ -31,6 +31,7 @@ def _torchrun(script, args, env_extra, timeout=300):
         env.pop(k, None)
     env.update(env_extra)
     env["CUDA_VISIBLE_DEVICES"] = ""
+    env["HIP_VISIBLE_DEVICES"] = ""
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
                         "--nproc-per-node=2", "--master-addr", "127.0.0.1",
                         f"--master-port={port}", str(REPO / script), *args],

@@ -99,7 +99,8 @@ def test_sharded_embedding_fwd_bwd(strategy, world, dp_dense):
 
 def _dlrm_worker(rank, world, B, steps, strategy, emb_opt="rowwise_adagrad", rw_comm="fp32",
                  pipeline=False, dense_comm="fp32", dist="uniform", alpha=1.05, rw_capacity=1.25,
-                 pipe_lookup=True, skew_from=None, pooling=(1, 2, 1, 1, 1), rw_exchange="auto"):
+                 pipe_lookup=True, skew_from=None, pooling=(1, 2, 1, 1, 1), rw_exchange="auto",
+                 dense_opt="adamw"):
     """skew_from: batches from this index on carry only even ids (every
     row-wise id of a 2-rank job then goes to owner 0)."""
     from tdfo_amd.data.synthetic import SyntheticCriteo
@@ -109,7 +110,8 @@ def _dlrm_worker(rank, world, B, steps, strategy, emb_opt="rowwise_adagrad", rw_
     cfg = DLRMConfig(embedding_dim=32, table_rows=ROWS, bottom=[64, 32], top=[64, 32, 1],
                      dense_lr=1e-2, emb_lr=0.05, sharding=strategy, pooling=list(pooling),
                      emb_opt=emb_opt, rw_comm=rw_comm, pipeline=pipeline, dense_comm=dense_comm,
-                     rw_capacity=rw_capacity, pipeline_lookup=pipe_lookup, rw_exchange=rw_exchange)
+                     rw_capacity=rw_capacity, pipeline_lookup=pipe_lookup, rw_exchange=rw_exchange,
+                     dense_opt=dense_opt)
     tr = DLRMTrainer(cfg, B, "cpu", group=get_info().group, rank=rank, world_size=world)
     assert tr.pipeline == (pipeline and world > 1)
     if tr.emb.rw_tables and rw_exchange != "auto":
@@ -249,14 +251,28 @@ def test_dlrm_lagged_rw_growth_is_exact():
     lagged check grows the capacity and redoes that batch's exchange before it
     is consumed -- parameters and tables equal the unpipelined run (capacity
     checked by a host read before every exchange) bit for bit, and one
-    process up to fp32 association."""
+    process up to fp32 association.
+
+    The one-process comparison runs the dense update with plain SGD: two
+    ranks sum the batch in another order than one process, and AdamW's
+    normalised update turns that rounding noise into steps of up to lr where
+    a gradient is ~0 (1.2e-3 after 5 steps on one CPU, 3e-8 on another).
+    Under SGD the difference stays at rounding level (parameters below 1,
+    each of 5 steps adds lr x a gradient whose sums differ in the last
+    bits: ~1e-8), so the bound is 2e-6 instead of 2e-4; a
+    dropped or misrouted lookup moves a parameter by lr x its gradient,
+    orders of magnitude more."""
     B, steps = 64, 5
     plain = run_distributed(_dlrm_worker, 2, B, steps, "row_wise", "rowwise_adagrad", "fp32", False,
                             "fp32", "uniform", 1.05, 1.25, True, 2)
     lag = run_distributed(_dlrm_worker, 2, B, steps, "row_wise", "rowwise_adagrad", "fp32", True,
                           "fp32", "uniform", 1.05, 1.25, True, 2)
+    lag_sgd = run_distributed(_dlrm_worker, 2, B, steps, "row_wise", "rowwise_adagrad", "fp32",
+                              True, "fp32", "uniform", 1.05, 1.25, True, 2, (1, 2, 1, 1, 1),
+                              "auto", "sgd")
     single = run_distributed(_dlrm_worker, 1, 2 * B, steps, "table_wise", "rowwise_adagrad", "fp32",
-                             False, "fp32", "uniform", 1.05, 1.25, True, 2)[0]
+                             False, "fp32", "uniform", 1.05, 1.25, True, 2, (1, 2, 1, 1, 1),
+                             "auto", "sgd")[0]
     for rank in range(2):
         p0, tabs0, g0, _ = plain[rank]
         p1, tabs1, g1, reads = lag[rank]
@@ -264,10 +280,13 @@ def test_dlrm_lagged_rw_growth_is_exact():
         assert torch.equal(p0, p1), (rank, (p0 - p1).abs().max())
         for t in tabs0:
             assert torch.equal(tabs0[t][2], tabs1[t][2]), (rank, t)
-        assert torch.allclose(p1, single[0], atol=2e-4)
-        for t, (lo, c0, w) in tabs1.items():
+        p2, tabs2, g2, reads2 = lag_sgd[rank]
+        assert g2 > 0 and reads2 >= steps - 1, (g2, reads2)
+        assert not torch.equal(p2, p1)                       # the SGD runs are their own
+        assert torch.allclose(p2, single[0], rtol=0, atol=2e-6), (rank, (p2 - single[0]).abs().max())
+        for t, (lo, c0, w) in tabs2.items():
             ref = single[1][t][2][slice(*lo)][:, c0:c0 + w.shape[1]]
-            assert torch.allclose(w, ref, atol=2e-4), (rank, t)
+            assert torch.allclose(w, ref, rtol=0, atol=2e-6), (rank, t, (w - ref).abs().max())
 
 
 @pytest.mark.parametrize("world,pipeline,skew", [(2, False, None), (3, False, None),
