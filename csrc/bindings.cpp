@@ -466,6 +466,75 @@ void rank_metrics(const Tensor& h, const Tensor& W, const Tensor& bias, const Te
                      part.data_ptr<float>(), out.data_ptr<float>(), cur_stream());
 }
 
+// Full-catalogue top-K search / full-ranking eval (retrieval.hip). Scratch is
+// allocated here, from the caching allocator, so the op is capturable.
+void topk_scores(const Tensor& q, const Tensor& W, const c10::optional<Tensor>& bias, int64_t k,
+                 const Tensor& out_ids, const Tensor& out_scores, int64_t v_lo, int64_t v_hi,
+                 const c10::optional<Tensor>& exclude, const c10::optional<Tensor>& target,
+                 const c10::optional<Tensor>& out_rank) {
+  check_f32c(q, "topk_scores: q"); check_f32c(W, "topk_scores: W");
+  check_f32c(out_scores, "topk_scores: out_scores");
+  check_dev(out_ids, "topk_scores: out_ids");
+  TORCH_CHECK(q.dim() == 2 && W.dim() == 2 && q.size(1) == W.size(1),
+              "topk_scores: q [B, E], W [V, E]");
+  const int64_t B = q.size(0), E = q.size(1), V = W.size(0);
+  TORCH_CHECK(E == 16 || E == 32 || E == 64, "topk_scores: E must be 16, 32 or 64");
+  TORCH_CHECK(V >= 1 && V <= INT32_MAX && B <= INT32_MAX, "topk_scores: 1 <= V < 2^31");
+  TORCH_CHECK(k >= 1 && k <= 128, "topk_scores: 1 <= k <= 128");
+  TORCH_CHECK(0 <= v_lo && v_lo <= v_hi && v_hi <= V, "topk_scores: 0 <= v_lo <= v_hi <= V");
+  TORCH_CHECK(aligned16(q.data_ptr()) && aligned16(W.data_ptr()),
+              "topk_scores: 16-B aligned rows");
+  TORCH_CHECK(out_ids.scalar_type() == at::kLong && out_ids.is_contiguous() &&
+              out_ids.dim() == 2 && out_ids.size(0) == B && out_ids.size(1) == k,
+              "topk_scores: out_ids int64 [B, k]");
+  TORCH_CHECK(out_scores.dim() == 2 && out_scores.size(0) == B && out_scores.size(1) == k,
+              "topk_scores: out_scores fp32 [B, k]");
+  const float* bp = nullptr;
+  if (bias.has_value()) {
+    check_f32c(*bias, "topk_scores: bias");
+    TORCH_CHECK(bias->numel() == V, "topk_scores: bias [V]");
+    bp = bias->data_ptr<float>();
+  }
+  const int64_t* ep = nullptr;
+  int64_t X = 0;
+  if (exclude.has_value()) {
+    check_dev(*exclude, "topk_scores: exclude");
+    TORCH_CHECK(exclude->scalar_type() == at::kLong && exclude->is_contiguous() &&
+                exclude->dim() == 2 && exclude->size(0) == B && exclude->size(1) <= INT32_MAX,
+                "topk_scores: exclude int64 [B, X]");
+    X = exclude->size(1);
+    if (X > 0) ep = exclude->data_ptr<int64_t>();
+  }
+  const int64_t* tp = nullptr;
+  int64_t* rp = nullptr;
+  TORCH_CHECK(target.has_value() == out_rank.has_value(),
+              "topk_scores: target and out_rank go together");
+  if (target.has_value()) {
+    check_dev(*target, "topk_scores: target"); check_dev(*out_rank, "topk_scores: out_rank");
+    TORCH_CHECK(target->scalar_type() == at::kLong && target->is_contiguous() &&
+                target->numel() == B, "topk_scores: target int64 [B]");
+    TORCH_CHECK(out_rank->scalar_type() == at::kLong && out_rank->is_contiguous() &&
+                out_rank->numel() == B, "topk_scores: out_rank int64 [B]");
+    tp = target->data_ptr<int64_t>();
+    rp = out_rank->data_ptr<int64_t>();
+  }
+  if (B == 0) return;
+  const tdfo::TopkPlan plan = tdfo::topk_plan((int)B, (int)v_lo, (int)v_hi);
+  Tensor part = at::empty({B * plan.S * k}, out_ids.options());
+  Tensor cpart, tscore, excl_ge;
+  if (tp != nullptr) {
+    cpart = at::empty({B * plan.S}, out_ids.options().dtype(at::kInt));
+    excl_ge = at::empty({B}, out_ids.options().dtype(at::kInt));
+    tscore = at::empty({B}, q.options());
+  }
+  tdfo::topk_scores(q.data_ptr<float>(), W.data_ptr<float>(), bp, ep, tp, (int)B, (int)V, (int)E,
+                    (int)X, (int)k, (int)v_lo, (int)v_hi, plan,
+                    reinterpret_cast<uint64_t*>(part.data_ptr<int64_t>()),
+                    tp ? cpart.data_ptr<int>() : nullptr, tp ? tscore.data_ptr<float>() : nullptr,
+                    tp ? excl_ge.data_ptr<int>() : nullptr, out_ids.data_ptr<int64_t>(),
+                    out_scores.data_ptr<float>(), rp, cur_stream());
+}
+
 // A HIP stream whose kernels may only use the CUs set in mask_words (bit i
 // of word w = CU 32 w + i). The embedding side stream uses it so its
 // memory-bound, many-block kernels leave CUs to the latency-bound GEMMs.
@@ -1753,6 +1822,10 @@ TORCH_LIBRARY(tdfo, m) {
         "Tensor rstd, float rate, int seed, Tensor? step, Tensor(a!) dx, Tensor(b!) part, "
         "Tensor(c!) out3, Tensor? gidx) -> ()");
   m.def("rank_metrics(Tensor h, Tensor W, Tensor bias, Tensor cand, int[] ks, Tensor(a!) out) -> ()");
+  m.def("topk_scores(Tensor q, Tensor W, Tensor? bias, int k, Tensor(a!) out_ids, "
+        "Tensor(b!) out_scores, int v_lo, int v_hi, Tensor? exclude, Tensor? target, "
+        "Tensor(c!)? out_rank) -> ()");
+  m.def("topk_splits(int n) -> int", [](int64_t n) { return (int64_t)tdfo::topk_splits((int)n); });
   m.def("layernorm_parts(int M) -> int", [](int64_t M) { return (int64_t)tdfo::layernorm_parts(M); });
   m.def("gather_columns(Tensor[] src, Tensor? idx, int row0, int n, Tensor(a!)[] dst, int[] dst_stride) -> ()");
   m.def("concat_features(Tensor dense, Tensor emb, int[] off, int[] stride, int F, int D, "
@@ -1858,6 +1931,7 @@ TORCH_LIBRARY_IMPL(tdfo, CUDA, m) {
   m.impl("layernorm_bwd", layernorm_bwd);
   m.impl("seq_prologue_fwd", seq_prologue_fwd);
   m.impl("rank_metrics", rank_metrics);
+  m.impl("topk_scores", topk_scores);
   m.impl("seq_prologue_bwd", seq_prologue_bwd);
   m.impl("gather_columns", gather_columns);
   m.impl("concat_features", concat_features);

@@ -96,6 +96,7 @@ class Config:
     resume: bool = False
     metrics_file: str = ""
     max_steps: int = 0
+    eval_full_ranking: bool = False   # bert4rec: also log full-catalogue full/Recall@k, full/NDCG@k
     profile_steps: str = ""           # "START:COUNT" -> roctx profile_window (§5.1)
     debug_checks: bool = False        # embedding id bounds checks on every lookup (§5.2)
     sharding: ShardingConfig = field(default_factory=ShardingConfig)

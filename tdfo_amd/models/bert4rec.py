@@ -548,6 +548,9 @@ class Bert4RecTrainer:
         self.loss_sum = torch.zeros(1, dtype=torch.float64, device=dev)
         self.steps = 0
         self.metric_sums = torch.zeros(len(METRIC_NAMES) + 1, dtype=torch.float64, device=dev)
+        # full-catalogue ranking sums (eval_batch_full), apart from the sampled ones
+        self.metric_sums_full = torch.zeros(len(METRIC_NAMES) + 1, dtype=torch.float64,
+                                            device=dev)
         self.graph = None
         self._static_loss = None
         # the step's counters (dense / embedding optimizer step numbers, the
@@ -718,6 +721,71 @@ class Bert4RecTrainer:
         if self.world > 1:
             dist.all_reduce(v, group=self.group)
         self.metric_sums.zero_()
+        n = max(1.0, float(v[-1]))
+        return {k: float(v[i]) / n for i, k in enumerate(METRIC_NAMES)}
+
+    # ------------------------------------------------- full-catalogue search
+    def _last_hidden(self, seqs: torch.Tensor) -> torch.Tensor:
+        """Last-position hidden state [B, E] of every sequence (eval mode)."""
+        self.model.eval()
+        self.item.eval()
+        B = seqs.shape[0]
+        if self.mode == "dmp" and B < self.B:     # sharded engine has a static shape
+            pad = torch.zeros(self.B - B, self.T, dtype=seqs.dtype, device=seqs.device)
+            seqs = torch.cat([seqs, pad])
+        h = self.model.encode(self._embed(seqs), seqs)[:B, -1, :].contiguous()
+        if h.is_cuda and self.E not in (16, 32, 64):
+            raise ValueError("full-catalogue search on the GPU needs embed_dim in (16, 32, 64)")
+        return h
+
+    @torch.no_grad()
+    def recommend(self, seqs: torch.Tensor, k: int, exclude_seen: bool = True):
+        """The k best items for every sequence [B, T] over the whole catalogue
+        (ids 1 .. n_items: PAD and MASK are not eligible), scored from the
+        last-position hidden state by the fused search (no [B, V] logits).
+        exclude_seen drops the items of the sequence itself. Returns
+        (ids int64 [B, k], scores fp32 [B, k]), best first, ties by lower id;
+        rows with fewer than k eligible items end in -1 / -inf."""
+        h = self._last_hidden(seqs)
+        B = h.shape[0]
+        ids = torch.empty(B, k, dtype=torch.int64, device=h.device)
+        scores = torch.empty(B, k, dtype=torch.float32, device=h.device)
+        # (the output layer is a replicated dense parameter in every mode,
+        # "dmp" included: only the input item table is sharded)
+        ops.topk_scores(h, self.model.out.weight.detach(), self.model.out.bias.detach(), k, ids,
+                        scores, 1, self.V - 1,
+                        exclude=seqs.contiguous() if exclude_seen else None)
+        return ids, scores
+
+    @torch.no_grad()
+    def eval_batch_full(self, seqs: torch.Tensor, targets: torch.Tensor,
+                        exclude_seen: bool = False):
+        """Full-ranking eval: rank of targets [B] among ALL items 1 .. n_items
+        (not 100 sampled negatives), pessimistic ties as in recall_ndcg_sums;
+        accumulates sums of their own (pop_metrics_full)."""
+        h = self._last_hidden(seqs)
+        B = h.shape[0]
+        ids = torch.empty(B, 1, dtype=torch.int64, device=h.device)
+        scores = torch.empty(B, 1, dtype=torch.float32, device=h.device)
+        rank = torch.empty(B, dtype=torch.int64, device=h.device)
+        ops.topk_scores(h, self.model.out.weight.detach(), self.model.out.bias.detach(), 1, ids,
+                        scores, 1, self.V - 1,
+                        exclude=seqs.contiguous() if exclude_seen else None,
+                        target=targets.to(torch.int64).contiguous(), out_rank=rank)
+        rec = [(rank < k).float().sum() for k in METRICS_K]
+        ndcg = [torch.where(rank < k, 1.0 / torch.log2(rank.float() + 2.0),
+                            torch.zeros_like(rank, dtype=torch.float32)).sum() for k in METRICS_K]
+        self.metric_sums_full[:-1] += torch.stack(rec + ndcg).double()
+        self.metric_sums_full[-1] += B
+        return rank
+
+    def pop_metrics_full(self) -> Dict[str, float]:
+        """Recall@k / NDCG@k of eval_batch_full since the last call (keys as
+        pop_metrics: prefix them when logging both)."""
+        v = self.metric_sums_full.clone()
+        if self.world > 1:
+            dist.all_reduce(v, group=self.group)
+        self.metric_sums_full.zero_()
         n = max(1.0, float(v[-1]))
         return {k: float(v[i]) / n for i, k in enumerate(METRIC_NAMES)}
 

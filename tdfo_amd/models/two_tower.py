@@ -103,6 +103,19 @@ def init_dense_params(init: str, seed: int) -> torch.Tensor:
     return torch.cat(parts)
 
 
+def catalogue_columns(cols: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """Item catalogue of a split: the item-side columns at the first occurrence
+    of every item_id, in ascending item_id order (row r of the result, and of
+    ``TwoTowerTrainer.item_vectors`` on it, is item ``result["item_id"][r]``)."""
+    item = torch.as_tensor(cols["item_id"]).to(torch.int64)
+    order = torch.sort(item, stable=True).indices
+    s = item[order]
+    first = torch.ones_like(s, dtype=torch.bool)
+    first[1:] = s[1:] != s[:-1]
+    rows = order[first]
+    return {f: torch.as_tensor(cols[f])[rows] for f in FEATURES[1:] + ["avg_rating", "num_pages"]}
+
+
 class TwoTowerTrainer:
     """Fused TwoTower training/eval engine (one rank)."""
 
@@ -499,6 +512,59 @@ class TwoTowerTrainer:
         ops.auc_hist(lg, y, self.nbins, self.eval_hist)
         self.n_seen += b
         return lg
+
+    # ------------------------------------------------------------ retrieval
+    def _table_rows(self, t: int, ids: torch.Tensor) -> torch.Tensor:
+        if self.sharded is not None:
+            return self.table_weight(t).to(self.device)[ids]
+        return self.emb.table_weight(t).detach()[ids]
+
+    def _tower(self, x: torch.Tensor, l1: str, l2: str) -> torch.Tensor:
+        if self.mp:
+            raise NotImplementedError("tower vectors are fp32: not for mixed_precision models")
+        p = ops.reference.two_tower_unpack(self.P[:NPARAM].detach())
+        z = x @ p[l1 + ".kernel"] + p[l1 + ".bias"]
+        return ((z * torch.sigmoid(z)) @ p[l2 + ".kernel"] + p[l2 + ".bias"]).contiguous()
+
+    @torch.no_grad()
+    def user_vectors(self, user_ids: torch.Tensor, chunk: int = 1 << 16) -> torch.Tensor:
+        """User tower output [n, 16] (Dense -> swish -> Dense of the user
+        embedding): logit(user, item) = user_vectors . item_vectors."""
+        user_ids = user_ids.to(self.device, torch.int64)
+        out = [self._tower(self._table_rows(0, user_ids[i: i + chunk]), "user_fc1", "user_fc2")
+               for i in range(0, user_ids.numel(), chunk)]
+        return torch.cat(out) if out else torch.zeros(0, E, device=self.device)
+
+    @torch.no_grad()
+    def item_vectors(self, cols: Dict[str, torch.Tensor], chunk: int = 1 << 16) -> torch.Tensor:
+        """Item tower output [n, 16] for rows of item columns (item_id, language,
+        is_ebook, format, publisher, pub_decade, avg_rating, num_pages)."""
+        n = int(cols["item_id"].shape[0])
+        out = []
+        for i in range(0, n, chunk):
+            c = {f: cols[f][i: i + chunk].to(self.device) for f in FEATURES[1:] +
+                 ["avg_rating", "num_pages"]}
+            x = torch.cat([self._table_rows(t, c[f].to(torch.int64))
+                           for t, f in enumerate(FEATURES) if t > 0] +
+                          [c["avg_rating"].float()[:, None], c["num_pages"].float()[:, None]], 1)
+            out.append(self._tower(x, "item_fc1", "item_fc2"))
+        return torch.cat(out) if out else torch.zeros(0, E, device=self.device)
+
+    @torch.no_grad()
+    def recommend(self, user_ids: torch.Tensor, item_vecs: torch.Tensor, k: int,
+                  exclude: Optional[torch.Tensor] = None):
+        """The k best rows of item_vecs [V, 16] (``item_vectors`` of a
+        catalogue) for every user, by the fused search: (row indices int64
+        [n, k], scores fp32 [n, k]), best first, ties by lower index, -1 / -inf
+        past the eligible rows. exclude: int64 [n, X] row indices per user that
+        may not be returned (entries < 0 are padding)."""
+        u = self.user_vectors(user_ids)
+        n = u.shape[0]
+        ids = torch.empty(n, k, dtype=torch.int64, device=u.device)
+        scores = torch.empty(n, k, dtype=torch.float32, device=u.device)
+        ops.topk_scores(u, item_vecs.contiguous(), None, k, ids, scores,
+                        exclude=None if exclude is None else exclude.to(u.device).contiguous())
+        return ids, scores
 
     # ------------------------------------------------------------ metrics
     def pop_metrics(self, eval_mode: bool = False, reduce: bool = True):

@@ -928,6 +928,36 @@ def rank_metrics(h, W, bias, cand, ks, out):
         ref.rank_metrics(h, W, bias, cand, ks, out)
 
 
+def topk_splits(n: int = -1) -> int:
+    """Ranges of V the top-K search is split over (csrc/kernels/retrieval.hip):
+    0 auto (default), n > 0 forces n (clamped to 64 and to the number of
+    128-item tiles); n < 0 only reads it. Returns the previous value. Results
+    do not depend on it."""
+    return int(_native().topk_splits(int(n)))
+
+
+def topk_scores(q, W, bias, k, out_ids, out_scores, v_lo=0, v_hi=None, exclude=None, target=None,
+                out_rank=None):
+    """Full-catalogue search without a [B, V] score tensor. Scores q [B, E] .
+    W [V, E] (+ bias [V]) in fp32 over the eligible items: ids in [v_lo, v_hi)
+    that are not in exclude[b] (int64 [B, X]; entries < 0 are padding,
+    duplicates allowed). out_ids int64 / out_scores fp32 [B, k] get the k <= 128
+    best of every row in the total order (score descending, id ascending),
+    padded with -1 / -inf where fewer are eligible.
+
+    With ``target`` (int64 [B], ids in [0, V)) out_rank[b] (int64) = number of
+    eligible items other than target[b] whose score is >= the target's (the
+    pessimistic tie rule of ``rank_metrics``). The target is scored like any
+    item even if it is in exclude[b] or outside [v_lo, v_hi): it is ranked as
+    if it were eligible. Scores must be finite."""
+    v_hi = W.shape[0] if v_hi is None else v_hi
+    if _gpu(q):
+        _native().topk_scores(q, W, bias, int(k), out_ids, out_scores, int(v_lo), int(v_hi),
+                              exclude, target, out_rank)
+    else:
+        ref.topk_scores(q, W, bias, k, out_ids, out_scores, v_lo, v_hi, exclude, target, out_rank)
+
+
 def seq_prologue_fwd(x, pos, n, eps, gamma, beta, rate, seed, step, y, mean, rstd):
     """y = dropout(LN(x + pos)) over rows of n (Bert4Rec input block); the
     dropout mask is a counter hash of (seed, step[0], row, element)."""

@@ -707,6 +707,68 @@ def rank_metrics(h, W, bias, cand, ks, out):
     out.copy_(torch.stack(rec + ndcg + [torch.tensor(float(h.shape[0]), device=h.device)]))
 
 
+TOPK_CHUNK = 4096     # items scored at a time by the top-K reference
+
+
+def topk_scores(q, W, bias, k, out_ids, out_scores, v_lo=0, v_hi=None, exclude=None, target=None,
+                out_rank=None):
+    """Reference of the fused top-K search (csrc/kernels/retrieval.hip): V in
+    chunks of TOPK_CHUNK, a running best-k per row. A stable descending sort of
+    [running best | chunk] keeps (score descending, id ascending): the running
+    ids are smaller than the chunk's and already in that order."""
+    B, V = q.shape[0], W.shape[0]
+    v_hi = V if v_hi is None else int(v_hi)
+    v_lo = int(v_lo)
+    if not (0 <= v_lo <= v_hi <= V and 1 <= k <= 128):
+        raise ValueError("topk_scores: 0 <= v_lo <= v_hi <= V, 1 <= k <= 128")
+    if (target is None) != (out_rank is None):
+        raise ValueError("topk_scores: target and out_rank go together")
+    dev = q.device
+    best_s = torch.full((B, k), float("-inf"), dtype=torch.float32, device=dev)
+    best_i = torch.full((B, k), -1, dtype=torch.int64, device=dev)
+
+    def chunk_scores(c0, c1):
+        s = q @ W[c0:c1].t()
+        return s + bias[c0:c1] if bias is not None else s
+
+    ts = None
+    if target is not None:
+        # the target's score out of the same chunk product every score comes from
+        ts = torch.full((B,), float("nan"), dtype=torch.float32, device=dev)
+        # ([v_lo, v_hi) in the chunks of the scoring pass below: a product of
+        # other shapes may round differently, and >= against it would not be
+        # bit-stable)
+        for lo, hi in ((v_lo, v_hi), (0, v_lo), (v_hi, V)):
+            for c0 in range(lo, hi, TOPK_CHUNK):
+                c1 = min(hi, c0 + TOPK_CHUNK)
+                rows = ((target >= c0) & (target < c1)).nonzero().flatten()
+                if rows.numel():
+                    ts[rows] = chunk_scores(c0, c1)[rows, target[rows] - c0]
+        rank = torch.zeros(B, dtype=torch.int64, device=dev)
+    for c0 in range(v_lo, v_hi, TOPK_CHUNK):
+        c1 = min(v_hi, c0 + TOPK_CHUNK)
+        s = chunk_scores(c0, c1)
+        ids = torch.arange(c0, c1, dtype=torch.int64, device=dev).expand(B, -1)
+        ok = torch.ones(B, c1 - c0, dtype=torch.bool, device=dev)
+        if exclude is not None and exclude.numel():
+            hit = ((exclude >= c0) & (exclude < c1)).nonzero()
+            ok[hit[:, 0], exclude[hit[:, 0], hit[:, 1]] - c0] = False
+        if target is not None:
+            rank += (ok & (ids != target[:, None]) & (s >= ts[:, None])).sum(1)
+        s = torch.where(ok, s, torch.full_like(s, float("-inf")))
+        ids = torch.where(ok, ids, torch.full_like(ids, -1))
+        # ineligible entries last among -inf ties: eligible scores are finite
+        cs = torch.cat([best_s, s], 1)
+        ci = torch.cat([best_i, ids], 1)
+        order = torch.sort(cs, dim=1, descending=True, stable=True).indices[:, :k]
+        best_s, best_i = cs.gather(1, order), ci.gather(1, order)
+    best_s = torch.where(best_i >= 0, best_s, torch.full_like(best_s, float("-inf")))
+    out_ids.copy_(best_i)
+    out_scores.copy_(best_s)
+    if target is not None:
+        out_rank.copy_(rank)
+
+
 def seq_prologue_mul(M: int, n: int, rate: float, seed: int, step: int, device):
     """[M, n] dropout multiplier of the fused sequence prologue
     (csrc/kernels/layernorm.hip::pro_mul)."""

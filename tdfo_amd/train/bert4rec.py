@@ -75,7 +75,12 @@ def run(cfg: Config, out_dir: str = ".", device: Optional[str] = None) -> List[D
             if b["seqs"].shape[0] == 0 and mode != "dmp":
                 continue
             tr.eval_batch(b["seqs"].to(dev), b["cand"].to(dev))
+            if cfg.eval_full_ranking:
+                # the positive (candidate 0) ranked against the whole catalogue
+                tr.eval_batch_full(b["seqs"].to(dev), b["cand"][:, 0].to(dev))
         m = tr.pop_metrics()
+        if cfg.eval_full_ranking:
+            m.update({"full/" + k: v for k, v in tr.pop_metrics_full().items()})
         if rank == 0:
             print(f"\nEpoch {epoch_idx + 1}, metrics {m}\n", flush=True)
         return m
