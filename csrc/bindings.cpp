@@ -227,7 +227,8 @@ tdfo::AttnArgs attn_args(const Tensor& qkv, const Tensor& ids, int64_t H, double
               ids.size(0) == qkv.size(0) && ids.size(1) == qkv.size(1), "attention: ids int64 [B, T]");
   const int64_t E3 = qkv.size(2);
   TORCH_CHECK(E3 % 3 == 0 && H > 0 && (E3 / 3) % H == 0, "attention: 3E must split into H heads");
-  TORCH_CHECK(qkv.size(1) <= 64, "attention: T <= 64");
+  TORCH_CHECK(qkv.size(1) <= tdfo::ATTN_LONG_MAXT,
+              "attention: T <= 512 (one-wave kernel up to 64, tiled kernel with lse above)");
   TORCH_CHECK(rate >= 0.0 && rate < 1.0, "attention: dropout rate in [0, 1)");
   tdfo::AttnArgs a{};
   a.qkv = qkv.data_ptr<float>(); a.ids = ids.data_ptr<int64_t>();
@@ -241,20 +242,41 @@ tdfo::AttnArgs attn_args(const Tensor& qkv, const Tensor& ids, int64_t H, double
   return a;
 }
 
+// the tiled kernels' row log-sum-exp [B, H, T] (T > 64 only; ignored below)
+void attn_lse(tdfo::AttnArgs& a, const c10::optional<Tensor>& lse) {
+  if (a.T <= tdfo::ATTN_SHORT_MAXT) return;
+  TORCH_CHECK(lse.has_value(), "attention: T > 64 needs lse fp32 [B, H, T]");
+  check_dev(*lse, "lse");
+  TORCH_CHECK(lse->scalar_type() == at::kFloat && lse->is_contiguous() &&
+              lse->numel() == (int64_t)a.B * a.H * a.T, "attention: lse fp32 [B, H, T]");
+  a.lse = lse->data_ptr<float>();
+}
+
 void attention_fwd(const Tensor& qkv, const Tensor& ids, int64_t H, double rate, int64_t seed,
-                   const c10::optional<Tensor>& step, int64_t pad_id, const Tensor& out) {
+                   const c10::optional<Tensor>& step, int64_t pad_id, const Tensor& out,
+                   const c10::optional<Tensor>& lse) {
   auto a = attn_args(qkv, ids, H, rate, seed, step, pad_id);
   check_dev(out, "out");
   TORCH_CHECK(out.scalar_type() == at::kFloat && out.is_contiguous() &&
               out.numel() == qkv.numel() / 3, "attention: out fp32 [B, T, E]");
   a.out = out.data_ptr<float>();
+  attn_lse(a, lse);
   tdfo::attention_fwd(a, cur_stream());
 }
 
 void attention_bwd(const Tensor& qkv, const Tensor& ids, const Tensor& dout, int64_t H,
                    double rate, int64_t seed, const c10::optional<Tensor>& step, int64_t pad_id,
-                   const Tensor& dqkv) {
+                   const Tensor& dqkv, const c10::optional<Tensor>& out,
+                   const c10::optional<Tensor>& lse) {
   auto a = attn_args(qkv, ids, H, rate, seed, step, pad_id);
+  if (a.T > tdfo::ATTN_SHORT_MAXT) {       // the tiled backward reads the forward's output
+    TORCH_CHECK(out.has_value(), "attention_bwd: T > 64 needs the forward's out [B, T, E]");
+    check_dev(*out, "out");
+    TORCH_CHECK(out->scalar_type() == at::kFloat && out->is_contiguous() &&
+                out->numel() == qkv.numel() / 3, "attention_bwd: out fp32 [B, T, E]");
+    a.out = out->data_ptr<float>();
+  }
+  attn_lse(a, lse);
   check_dev(dout, "dout"); check_dev(dqkv, "dqkv");
   TORCH_CHECK(dout.scalar_type() == at::kFloat && dout.is_contiguous() &&
               dout.numel() == qkv.numel() / 3, "attention: dout fp32 [B, T, E]");
@@ -366,7 +388,8 @@ void layernorm_fwd(const Tensor& x, int64_t n, double eps, const Tensor& gamma, 
                    const Tensor& y, const Tensor& mean, const Tensor& rstd) {
   check_f32c(x, "x"); check_f32c(gamma, "gamma"); check_f32c(beta, "beta");
   check_f32c(y, "y"); check_f32c(mean, "mean"); check_f32c(rstd, "rstd");
-  TORCH_CHECK(n > 0 && n <= 1024 && x.numel() % n == 0, "layernorm: n in (0, 1024] dividing x");
+  TORCH_CHECK(n > 0 && n <= tdfo::LN_WIDE_MAXN && x.numel() % n == 0,
+              "layernorm: n in (0, 32768] dividing x");
   const int64_t M = x.numel() / n;
   TORCH_CHECK(gamma.numel() == n && beta.numel() == n && y.numel() == x.numel() &&
               mean.numel() >= M && rstd.numel() >= M, "layernorm: shapes");
@@ -380,11 +403,13 @@ void layernorm_bwd(const Tensor& x, const Tensor& g, int64_t n, const Tensor& ga
                    const Tensor& dgb) {
   check_f32c(x, "x"); check_f32c(g, "g"); check_f32c(gamma, "gamma"); check_f32c(mean, "mean");
   check_f32c(rstd, "rstd"); check_f32c(dx, "dx"); check_f32c(part, "part"); check_f32c(dgb, "dgb");
-  TORCH_CHECK(n > 0 && n <= 1024 && x.numel() % n == 0, "layernorm: n");
+  TORCH_CHECK(n > 0 && n <= tdfo::LN_WIDE_MAXN && x.numel() % n == 0,
+              "layernorm: n in (0, 32768] dividing x");
   const int64_t M = x.numel() / n;
   TORCH_CHECK(g.numel() == x.numel() && dx.numel() == x.numel() && gamma.numel() == n &&
               mean.numel() >= M && rstd.numel() >= M && dgb.numel() == 2 * n &&
-              part.numel() >= (int64_t)tdfo::layernorm_parts(M) * 2 * n, "layernorm_bwd: shapes");
+              (n > tdfo::LN_NARROW_MAXN ||            // (wide rows do not use part)
+               part.numel() >= (int64_t)tdfo::layernorm_parts(M) * 2 * n), "layernorm_bwd: shapes");
   tdfo::layernorm_bwd(x.data_ptr<float>(), g.data_ptr<float>(), M, (int)n, gamma.data_ptr<float>(),
                       mean.data_ptr<float>(), rstd.data_ptr<float>(), dx.data_ptr<float>(),
                       part.data_ptr<float>(), dgb.data_ptr<float>(), cur_stream());
@@ -396,7 +421,8 @@ void seq_prologue_fwd(const Tensor& x, const Tensor& pos, int64_t n, double eps,
                       const Tensor& rstd) {
   check_f32c(x, "x"); check_f32c(pos, "pos"); check_f32c(gamma, "gamma"); check_f32c(beta, "beta");
   check_f32c(y, "y"); check_f32c(mean, "mean"); check_f32c(rstd, "rstd");
-  TORCH_CHECK(n > 0 && n <= 1024 && x.numel() % n == 0, "seq_prologue: n in (0, 1024] dividing x");
+  TORCH_CHECK(n > 0 && n <= tdfo::LN_WIDE_MAXN && x.numel() % n == 0,
+              "seq_prologue: n in (0, 32768] dividing x");
   const int64_t M = x.numel() / n;
   TORCH_CHECK(pos.numel() == n && gamma.numel() == n && beta.numel() == n &&
               y.numel() == x.numel() && mean.numel() >= M && rstd.numel() >= M,
@@ -420,12 +446,14 @@ void seq_prologue_bwd(const Tensor& x, const Tensor& pos, const Tensor& g, int64
   check_f32c(x, "x"); check_f32c(pos, "pos"); check_f32c(g, "g"); check_f32c(gamma, "gamma");
   check_f32c(mean, "mean"); check_f32c(rstd, "rstd"); check_f32c(dx, "dx");
   check_f32c(part, "part"); check_f32c(out3, "out3");
-  TORCH_CHECK(n > 0 && n <= 1024 && x.numel() % n == 0, "seq_prologue: n");
+  TORCH_CHECK(n > 0 && n <= tdfo::LN_WIDE_MAXN && x.numel() % n == 0,
+              "seq_prologue: n in (0, 32768] dividing x");
   const int64_t M = x.numel() / n;
   TORCH_CHECK(pos.numel() == n && g.numel() == x.numel() && dx.numel() == x.numel() &&
               gamma.numel() == n && mean.numel() >= M && rstd.numel() >= M &&
               (gidx ? out3.numel() >= 3 * n : out3.numel() == 3 * n) &&
-              part.numel() >= (int64_t)tdfo::layernorm_parts(M) * 3 * n, "seq_prologue_bwd: shapes");
+              (n > tdfo::LN_NARROW_MAXN ||
+               part.numel() >= (int64_t)tdfo::layernorm_parts(M) * 3 * n), "seq_prologue_bwd: shapes");
   const int64_t* sp = nullptr;
   if (step) {
     check_dev(*step, "step");
@@ -1611,11 +1639,12 @@ void linear_xent(const Tensor& H, const Tensor& W, const Tensor& bias, const Ten
                  const std::vector<Tensor>& ostate, const c10::optional<Tensor>& ohyper,
                  const std::vector<double>& oparams, int64_t okind) {
   check_dev(H, "H");
-  TORCH_CHECK(H.scalar_type() == at::kFloat && H.dim() == 2 && H.size(1) == 16 &&
-              H.is_contiguous() && aligned16(H.data_ptr()), "linear_xent: H fp32 [N,16]");
-  const int64_t N = H.size(0), V = W.size(0);
-  TORCH_CHECK(W.scalar_type() == at::kFloat && W.dim() == 2 && W.size(1) == 16 &&
-              W.is_contiguous() && aligned16(W.data_ptr()), "linear_xent: W fp32 [V,16]");
+  TORCH_CHECK(H.scalar_type() == at::kFloat && H.dim() == 2 &&
+              (H.size(1) == 16 || H.size(1) == 32 || H.size(1) == 64) &&
+              H.is_contiguous() && aligned16(H.data_ptr()), "linear_xent: H fp32 [N,16|32|64]");
+  const int64_t N = H.size(0), V = W.size(0), E = H.size(1);
+  TORCH_CHECK(W.scalar_type() == at::kFloat && W.dim() == 2 && W.size(1) == E &&
+              W.is_contiguous() && aligned16(W.data_ptr()), "linear_xent: W fp32 [V,E]");
   TORCH_CHECK(bias.scalar_type() == at::kFloat && bias.numel() == V && bias.is_contiguous(),
               "linear_xent: bias [V]");
   TORCH_CHECK(labels.scalar_type() == at::kLong && labels.numel() == N && labels.is_contiguous(),
@@ -1656,7 +1685,7 @@ void linear_xent(const Tensor& H, const Tensor& W, const Tensor& bias, const Ten
     for (int k = 0; k < 4; ++k) {
       check_dev(ostate[k], "ostate");
       TORCH_CHECK(ostate[k].scalar_type() == at::kFloat && ostate[k].is_contiguous() &&
-                  ostate[k].numel() == (k < 2 ? V * 16 : V) && aligned16(ostate[k].data_ptr()),
+                  ostate[k].numel() == (k < 2 ? V * E : V) && aligned16(ostate[k].data_ptr()),
                   "linear_xent: moments");
     }
     check_dev(*ohyper, "ohyper");
@@ -1669,6 +1698,13 @@ void linear_xent(const Tensor& H, const Tensor& W, const Tensor& bias, const Ten
     a.ohyper = ohyper->data_ptr<float>();
     a.beta1 = (float)oparams[0]; a.beta2 = (float)oparams[1];
     a.oeps = (float)oparams[2]; a.owd = (float)oparams[3];
+  }
+  if (E != 16) {                   // hidden 32 / 64: linear_xent_wide.hip
+    Tensor ws = at::empty({(int64_t)tdfo::linear_xent_wide_workspace((int)N, V, (int)E)},
+                          H.options().dtype(at::kByte));
+    a.workspace = ws.data_ptr();
+    tdfo::linear_xent_wide(a, (int)E, cur_stream());
+    return;
   }
   Tensor ws = at::empty({(int64_t)tdfo::linear_xent_workspace((int)N, V)},
                         H.options().dtype(at::kByte));
@@ -1809,9 +1845,9 @@ TORCH_LIBRARY(tdfo, m) {
         "Tensor(b!) part, Tensor(c!) grad, Tensor? gidx, bool defer=False) -> ()");
   m.def("encoder_reduce_flush() -> ()", encoder_reduce_flush);
   m.def("attention_fwd(Tensor qkv, Tensor ids, int H, float rate, int seed, Tensor? step, int pad_id, "
-        "Tensor(a!) out) -> ()");
+        "Tensor(a!) out, Tensor(b!)? lse=None) -> ()");
   m.def("attention_bwd(Tensor qkv, Tensor ids, Tensor dout, int H, float rate, int seed, Tensor? step, "
-        "int pad_id, Tensor(a!) dqkv) -> ()");
+        "int pad_id, Tensor(a!) dqkv, Tensor? out=None, Tensor? lse=None) -> ()");
   m.def("layernorm_fwd(Tensor x, int n, float eps, Tensor gamma, Tensor beta, Tensor(a!) y, "
         "Tensor(b!) mean, Tensor(c!) rstd) -> ()");
   m.def("layernorm_bwd(Tensor x, Tensor g, int n, Tensor gamma, Tensor mean, Tensor rstd, "

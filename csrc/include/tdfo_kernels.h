@@ -462,6 +462,11 @@ struct LinearXentArgs {
   float beta1 = 0.9f, beta2 = 0.999f, oeps = 1e-8f, owd = 0.f;
 };
 size_t linear_xent_workspace(int N, int64_t V);
+// Hidden widths 32 and 64 (linear_xent_wide.hip: Bert4Rec at the published
+// hidden size): the same contract with H [N,E], W [V,E], moments [V,E], on
+// VALU kernels (the MFMA kernels of linear_xent.hip are built around E = 16).
+size_t linear_xent_wide_workspace(int N, int64_t V, int E);
+void linear_xent_wide(const LinearXentArgs& a, int E, hipStream_t s);
 // 1: f32-input MFMA pass1/wgrad (default), 0: VALU kernels; <0 queries.
 // Returns the previous setting.
 int linear_xent_impl(int impl);
@@ -475,9 +480,19 @@ struct AttnArgs {
   const float* qkv; const int64_t* ids;
   const float* dout; float* out; float* dqkv;
   int B, T, H, dk; float scale, rate; int64_t seed; const int64_t* step; int64_t pad_id;
+  float* lse = nullptr;        // [B,H,T] row log-sum-exp, long-T path only (fwd writes, bwd reads)
 };
+// T <= 64: attention.hip (one wave per (sample, head)); 64 < T <= 512: the
+// tiled kernels below, which also need lse (and, backward, the forward's out).
 void attention_fwd(const AttnArgs& a, hipStream_t s);
 void attention_bwd(const AttnArgs& a, hipStream_t s);
+// Tiled long-T core (attention_long.hip): 64-query x 64-key tiles on the f32
+// MFMA, online softmax, nothing of size [B,H,T,T] in HBM, no atomics. Same
+// maths, layouts and dropout hash; the hash keys a row by (b*H+h)*512 + i.
+constexpr int ATTN_SHORT_MAXT = 64;
+constexpr int ATTN_LONG_MAXT = 512;
+void attention_long_fwd(const AttnArgs& a, hipStream_t s);
+void attention_long_bwd(const AttnArgs& a, hipStream_t s);
 
 // --------------------------------------------------- encoder layer ----
 // Fused Bert4Rec transformer block (encoder.hip), fp32, one workgroup per
@@ -541,7 +556,11 @@ void rank_metrics(const float* h, const float* W, const float* bias, const int64
                   hipStream_t s);
 
 // ------------------------------------------------------- layernorm ----
-// Row LayerNorm over the last n <= 1024 elements (layernorm.hip).
+// Row LayerNorm over the last n elements (layernorm.hip). n <= 1024: one wave
+// per row; 1024 < n <= 32768 (wide rows): one workgroup per row, and the
+// parameter gradients from a column-parallel pass over the rows (`part` unused).
+constexpr int LN_NARROW_MAXN = 1024;
+constexpr int LN_WIDE_MAXN = 32768;
 int layernorm_parts(int64_t M);
 void layernorm_fwd(const float* x, int64_t M, int n, float eps, const float* gamma,
                    const float* beta, float* y, float* mean, float* rstd, hipStream_t s);

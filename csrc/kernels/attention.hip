@@ -199,14 +199,14 @@ __global__ __launch_bounds__(64) void attn_bwd_kernel(AttnArgs a) {
 
 void attention_fwd(const AttnArgs& a, hipStream_t s) {
   if (a.B <= 0) return;
-  if (a.T > AT_MAXT) throw std::runtime_error("attention: T > 64");
+  if (a.T > AT_MAXT) { attention_long_fwd(a, s); return; }   // tiled path (attention_long.hip)
   TDFO_ATTN_DISPATCH(attn_fwd_kernel);
   TDFO_CHECK_HIP(hipGetLastError());
 }
 
 void attention_bwd(const AttnArgs& a, hipStream_t s) {
   if (a.B <= 0) return;
-  if (a.T > AT_MAXT) throw std::runtime_error("attention: T > 64");
+  if (a.T > AT_MAXT) { attention_long_bwd(a, s); return; }
   TDFO_ATTN_DISPATCH(attn_bwd_kernel);
   TDFO_CHECK_HIP(hipGetLastError());
 }

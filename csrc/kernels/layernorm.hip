@@ -161,6 +161,123 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x
   }
 }
 
+// ---- wide rows, 1024 < n <= 32768 (Bert4Rec's joint [T, E] LayerNorm at the
+// published shapes: n = 3200 at max_len 50, 12800 at 200). There are only
+// M = batch rows, so one workgroup owns a row; the row is re-read from L1/L2
+// (<= 128 KiB) instead of held in registers. Statistics are block reductions
+// in a fixed order. The parameter gradients come from a column-parallel pass
+// (one thread per element, rows in ascending order: deterministic) instead of
+// the [blocks][3n] partial buffer + reduce_rows of the narrow path, which
+// would be tens of MB here; `part` is unused.
+constexpr int LNW_THREADS = 64 * LN_WAVES;
+
+// sum over the workgroup, the same value in every thread: wave sums, then the
+// waves in order
+__device__ __forceinline__ float lnw_block_sum(float v, float* red) {
+  v = wave_sum(v);
+  __syncthreads();                                  // red may still be read
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float s = 0.f;
+#pragma unroll
+  for (int q = 0; q < LN_WAVES; ++q) s += red[q];
+  return s;
+}
+
+template <bool PRO>
+__global__ __launch_bounds__(LNW_THREADS) void ln_wide_fwd_kernel(
+    const float* __restrict__ x, int n, float eps, const float* __restrict__ gamma,
+    const float* __restrict__ beta, float* __restrict__ y, float* __restrict__ mean,
+    float* __restrict__ rstd, ProArgs pa) {
+  __shared__ float red[LN_WAVES];
+  const int64_t r = blockIdx.x;
+  const float* xr = x + r * n;
+  const float invn = 1.f / (float)n;
+  const uint32_t sd = PRO ? pro_seed(pa) : 0u;
+  float s = 0.f;
+  for (int e = threadIdx.x; e < n; e += LNW_THREADS) s += xr[e] + (PRO ? pa.pos[e] : 0.f);
+  const float mu = lnw_block_sum(s, red) * invn;
+  float q = 0.f;
+  for (int e = threadIdx.x; e < n; e += LNW_THREADS) {
+    const float d = xr[e] + (PRO ? pa.pos[e] : 0.f) - mu;
+    q += d * d;
+  }
+  const float rs = rsqrtf(lnw_block_sum(q, red) * invn + eps);
+  float* yr = y + r * n;
+  for (int e = threadIdx.x; e < n; e += LNW_THREADS) {
+    const float v = xr[e] + (PRO ? pa.pos[e] : 0.f);
+    const float o = (v - mu) * rs * gamma[e] + beta[e];
+    yr[e] = PRO ? o * pro_mul(pa, sd, r, e) : o;
+  }
+  if (threadIdx.x == 0) { mean[r] = mu; rstd[r] = rs; }
+}
+
+// dx of one row per workgroup
+template <bool PRO>
+__global__ __launch_bounds__(LNW_THREADS) void ln_wide_dx_kernel(
+    const float* __restrict__ x, const float* __restrict__ g, int n,
+    const float* __restrict__ gamma, const float* __restrict__ mean,
+    const float* __restrict__ rstd, float* __restrict__ dx, ProArgs pa) {
+  __shared__ float red[LN_WAVES];
+  const int64_t r = blockIdx.x;
+  const float* xr = x + r * n;
+  const float* gr = g + r * n;
+  const float invn = 1.f / (float)n, mu = mean[r], rs = rstd[r];
+  const uint32_t sd = PRO ? pro_seed(pa) : 0u;
+  float s1 = 0.f, s2 = 0.f;
+  for (int e = threadIdx.x; e < n; e += LNW_THREADS) {
+    const float gv = PRO ? gr[e] * pro_mul(pa, sd, r, e) : gr[e];
+    const float xh = (xr[e] + (PRO ? pa.pos[e] : 0.f) - mu) * rs;
+    const float gg = gv * gamma[e];
+    s1 += gg;
+    s2 += gg * xh;
+  }
+  const float m1 = lnw_block_sum(s1, red) * invn;
+  const float m2 = lnw_block_sum(s2, red) * invn;
+  float* dr = dx + r * n;
+  for (int e = threadIdx.x; e < n; e += LNW_THREADS) {
+    const float gv = PRO ? gr[e] * pro_mul(pa, sd, r, e) : gr[e];
+    const float xh = (xr[e] + (PRO ? pa.pos[e] : 0.f) - mu) * rs;
+    dr[e] = rs * (gv * gamma[e] - m1 - xh * m2);
+  }
+}
+
+// out[e] = dgamma, out[n + e] = dbeta (, out[2n + e] = dpos = sum of dx over the
+// rows): thread e walks the M rows in order, coalesced across e. idx: the
+// write-through into a flat gradient buffer, as reduce_rows(..., idx) (the
+// value overwrites). Blocks >= nb run a parked encoder reduction's columns.
+template <bool PRO>
+__global__ __launch_bounds__(LNW_THREADS) void ln_wide_col_kernel(
+    const float* __restrict__ x, const float* __restrict__ g, int64_t M, int n,
+    const float* __restrict__ mean, const float* __restrict__ rstd,
+    const float* __restrict__ dx, float* __restrict__ out, const int64_t* __restrict__ idx,
+    ProArgs pa, int nb, EncRedJob job) {
+  if ((int)blockIdx.x >= nb) {
+    enc_red_col(job, ((int)blockIdx.x - nb) * (int)blockDim.x + (int)threadIdx.x);
+    return;
+  }
+  const int e = (int)blockIdx.x * LNW_THREADS + (int)threadIdx.x;
+  if (e >= n) return;
+  const uint32_t sd = PRO ? pro_seed(pa) : 0u;
+  const float pe = PRO ? pa.pos[e] : 0.f;
+  float dg = 0.f, db = 0.f, dp = 0.f;
+#pragma unroll 4
+  for (int64_t r = 0; r < M; ++r) {
+    const float gv = PRO ? g[r * n + e] * pro_mul(pa, sd, r, e) : g[r * n + e];
+    const float xh = (x[r * n + e] + pe - mean[r]) * rstd[r];
+    dg += gv * xh;
+    db += gv;
+    if (PRO) dp += dx[r * n + e];
+  }
+  out[idx ? idx[e] : e] = dg;
+  out[idx ? idx[n + e] : n + e] = db;
+  if (PRO) out[idx ? idx[2 * n + e] : 2 * n + e] = dp;
+}
+
+void ln_check_wide(int n) {
+  if (n > LN_WIDE_MAXN) throw std::runtime_error("layernorm: n > 32768");
+}
+
 }  // namespace
 
 int layernorm_parts(int64_t M) {
@@ -182,6 +299,13 @@ int layernorm_parts(int64_t M) {
 void layernorm_fwd(const float* x, int64_t M, int n, float eps, const float* gamma,
                    const float* beta, float* y, float* mean, float* rstd, hipStream_t s) {
   if (M <= 0) return;
+  if (n > LN_NARROW_MAXN) {
+    ln_check_wide(n);
+    hipLaunchKernelGGL((ln_wide_fwd_kernel<false>), dim3((unsigned)M), dim3(LNW_THREADS), 0, s, x,
+                       n, eps, gamma, beta, y, mean, rstd, ProArgs{});
+    TDFO_CHECK_HIP(hipGetLastError());
+    return;
+  }
   const dim3 grid(layernorm_parts(M)), block(64 * LN_WAVES);
   TDFO_LN_DISPATCH(ln_fwd_kernel, false, grid, block, 0, s, x, M, n, eps, gamma, beta, y, mean,
                    rstd, ProArgs{});
@@ -192,6 +316,17 @@ void layernorm_bwd(const float* x, const float* g, int64_t M, int n, const float
                    const float* mean, const float* rstd, float* dx, float* part,
                    float* dgamma_dbeta, hipStream_t s) {
   if (M <= 0) return;
+  if (n > LN_NARROW_MAXN) {
+    ln_check_wide(n);
+    const int cb = (n + LNW_THREADS - 1) / LNW_THREADS;
+    hipLaunchKernelGGL((ln_wide_dx_kernel<false>), dim3((unsigned)M), dim3(LNW_THREADS), 0, s, x,
+                       g, n, gamma, mean, rstd, dx, ProArgs{});
+    hipLaunchKernelGGL((ln_wide_col_kernel<false>), dim3(cb), dim3(LNW_THREADS), 0, s, x, g, M, n,
+                       mean, rstd, dx, dgamma_dbeta, (const int64_t*)nullptr, ProArgs{}, cb,
+                       EncRedJob{});
+    TDFO_CHECK_HIP(hipGetLastError());
+    return;
+  }
   const int nb = layernorm_parts(M);
   const dim3 grid(nb), block(64 * LN_WAVES);
   TDFO_LN_DISPATCH(ln_bwd_kernel, false, grid, block, 0, s, x, g, M, n, gamma, mean, rstd, dx,
@@ -204,8 +339,15 @@ void seq_prologue_fwd(const float* x, const float* pos, int64_t M, int n, float 
                       const float* gamma, const float* beta, float rate, uint32_t seed,
                       const int64_t* step, float* y, float* mean, float* rstd, hipStream_t s) {
   if (M <= 0) return;
-  const dim3 grid(layernorm_parts(M)), block(64 * LN_WAVES);
   const ProArgs pa{pos, rate, seed, step};
+  if (n > LN_NARROW_MAXN) {
+    ln_check_wide(n);
+    hipLaunchKernelGGL((ln_wide_fwd_kernel<true>), dim3((unsigned)M), dim3(LNW_THREADS), 0, s, x,
+                       n, eps, gamma, beta, y, mean, rstd, pa);
+    TDFO_CHECK_HIP(hipGetLastError());
+    return;
+  }
+  const dim3 grid(layernorm_parts(M)), block(64 * LN_WAVES);
   TDFO_LN_DISPATCH(ln_fwd_kernel, true, grid, block, 0, s, x, M, n, eps, gamma, beta, y, mean,
                    rstd, pa);
   TDFO_CHECK_HIP(hipGetLastError());
@@ -216,13 +358,29 @@ void seq_prologue_bwd(const float* x, const float* pos, const float* g, int64_t 
                       uint32_t seed, const int64_t* step, float* dx, float* part,
                       float* dgamma_dbeta_dpos, hipStream_t s, const int64_t* idx) {
   if (M <= 0) return;
+  const ProArgs pa{pos, rate, seed, step};
+  if (n > LN_NARROW_MAXN) {
+    ln_check_wide(n);
+    // A parked encoder reduction is taken here exactly as on the narrow path
+    // (extra blocks of the column pass). The fused block does not fit its LDS
+    // budget at these row widths today, so nothing is normally parked, but the
+    // job must not be dropped if that ever changes.
+    EncRedJob job;
+    const int extra = encoder_reduce_take(&job) ? (job.P + LNW_THREADS - 1) / LNW_THREADS : 0;
+    const int cb = (n + LNW_THREADS - 1) / LNW_THREADS;
+    hipLaunchKernelGGL((ln_wide_dx_kernel<true>), dim3((unsigned)M), dim3(LNW_THREADS), 0, s, x, g,
+                       n, gamma, mean, rstd, dx, pa);
+    hipLaunchKernelGGL((ln_wide_col_kernel<true>), dim3(cb + extra), dim3(LNW_THREADS), 0, s, x, g,
+                       M, n, mean, rstd, dx, dgamma_dbeta_dpos, idx, pa, cb, job);
+    TDFO_CHECK_HIP(hipGetLastError());
+    return;
+  }
   const int nb = layernorm_parts(M);
   // the last encoder layer's parked parameter-gradient reduction, if any,
   // rides in extra blocks of this launch
   EncRedJob job;
   const int extra = encoder_reduce_take(&job) ? (job.P + 64 * LN_WAVES - 1) / (64 * LN_WAVES) : 0;
   const dim3 grid(nb + extra), block(64 * LN_WAVES);
-  const ProArgs pa{pos, rate, seed, step};
   TDFO_LN_DISPATCH(ln_bwd_kernel, true, grid, block, 0, s, x, g, M, n, gamma, mean, rstd, dx,
                    part, pa, nb, job);
   TDFO_CHECK_HIP(hipGetLastError());

@@ -1,6 +1,9 @@
 #!/usr/bin/env python
 """Bert4Rec training throughput on one GPU (reference config: per-device batch
-16, T=20, E=16, 2 heads, 2 layers) with a Goodreads-scale vocabulary."""
+16, T=20, E=16, 2 heads, 2 layers) with a Goodreads-scale vocabulary.
+--max-len / --embed-dim / --heads / --layers pick another shape, e.g. the
+published BERT4Rec one: --max-len 200 --embed-dim 64 (T > 64 runs the tiled
+attention and wide LayerNorm kernels; the fused block covers T <= 64)."""
 import argparse
 import json
 import sys
@@ -19,6 +22,10 @@ def main():
     ap.add_argument("--items", type=int, default=1_000_000)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--max-len", type=int, default=20)
+    ap.add_argument("--embed-dim", type=int, default=16)
+    ap.add_argument("--heads", type=int, default=2)
+    ap.add_argument("--layers", type=int, default=2)
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--torch-encoder", action="store_true",
                     help="torch reference attention/LayerNorm instead of the HIP kernels")
@@ -27,8 +34,8 @@ def main():
         import tdfo_amd.models.bert4rec as m
         m.USE_FUSED = False
     dev = "cuda"
-    T = 20
-    tr = Bert4RecTrainer(a.items, T, 16, 2, 2, a.batch, device=dev)
+    T = a.max_len
+    tr = Bert4RecTrainer(a.items, T, a.embed_dim, a.heads, a.layers, a.batch, device=dev)
     g = torch.Generator(device=dev).manual_seed(0)
     pool = []
     for _ in range(8):
@@ -51,6 +58,8 @@ def main():
     torch.cuda.synchronize()
     el = time.perf_counter() - t
     print(json.dumps({"model": "bert4rec", "batch": a.batch, "vocab": a.items + 2,
+                      "max_len": T, "embed_dim": a.embed_dim, "heads": a.heads,
+                      "layers": a.layers,
                       "graph": not a.no_graph, "fused_encoder": not a.torch_encoder, "ms_per_step": round(el / a.steps * 1e3, 4),
                       "sequences_per_sec": round(a.batch * a.steps / el, 1),
                       "loss": round(tr.pop_loss(), 4)}))

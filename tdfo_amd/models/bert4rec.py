@@ -46,7 +46,9 @@ METRICS_K = (10, 20, 50)
 # ---------------------------------------------------- fused HIP encoder ops
 # On GPU the attention core (scores, key-padding mask, softmax, dropout, P.V)
 # and every LayerNorm run as hand-written kernels (csrc/kernels/attention.hip,
-# layernorm.hip); on CPU the same modules run the torch reference ops.
+# attention_long.hip above T = 64, layernorm.hip); on CPU the same modules run
+# the torch reference ops. Supported on the GPU: max_len <= 512, embed_dim in
+# {16, 32, 64}, embed_dim / heads in {4, 8, 16, 32, 64}, max_len * embed_dim <= 32768.
 USE_FUSED = True
 # whole transformer block in one fwd / one bwd kernel (encoder.hip); False
 # keeps the per-op path (fused attention core + LayerNorm kernels, torch GEMMs)
@@ -66,17 +68,29 @@ class _AttnCoreFn(torch.autograd.Function):
         qkv = qkv.contiguous()
         B, T, E3 = qkv.shape
         out = torch.empty(B, T, E3 // 3, dtype=qkv.dtype, device=qkv.device)
-        ops.attention_fwd(qkv, ids, H, rate, seed, step, PAD_ID, out)
-        ctx.save_for_backward(qkv, ids, step)
+        if T > ops.ATTN_SHORT_MAXT:
+            # tiled kernels: the backward recomputes P from the saved row
+            # log-sum-exp and takes rowsum(P o dP) from dO . O
+            lse = torch.empty(B, H, T, dtype=torch.float32, device=qkv.device)
+            ops.attention_fwd(qkv, ids, H, rate, seed, step, PAD_ID, out, lse=lse)
+            ctx.save_for_backward(qkv, ids, step, out, lse)
+        else:
+            ops.attention_fwd(qkv, ids, H, rate, seed, step, PAD_ID, out)
+            ctx.save_for_backward(qkv, ids, step)
         ctx.cfg = (H, rate, seed)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        qkv, ids, step = ctx.saved_tensors
+        qkv, ids, step = ctx.saved_tensors[:3]
         H, rate, seed = ctx.cfg
         dqkv = torch.empty_like(qkv)
-        ops.attention_bwd(qkv, ids, g.contiguous(), H, rate, seed, step, PAD_ID, dqkv)
+        if len(ctx.saved_tensors) > 3:
+            out, lse = ctx.saved_tensors[3:]
+            ops.attention_bwd(qkv, ids, g.contiguous(), H, rate, seed, step, PAD_ID, dqkv,
+                              out=out, lse=lse)
+        else:
+            ops.attention_bwd(qkv, ids, g.contiguous(), H, rate, seed, step, PAD_ID, dqkv)
         return dqkv, None, None, None, None, None
 
 
@@ -99,7 +113,7 @@ class _LayerNormFn(torch.autograd.Function):
         n = ctx.n
         M = x.numel() // n
         dx = torch.empty_like(x)
-        part = torch.empty(ops.layernorm_parts(M) * 2 * n, dtype=torch.float32, device=x.device)
+        part = torch.empty(ops.layernorm_parts(M, n) * 2 * n, dtype=torch.float32, device=x.device)
         dgb = torch.empty(2 * n, dtype=torch.float32, device=x.device)
         ops.layernorm_bwd(x, g.contiguous(), n, gamma, mean, rstd, dx, part, dgb)
         return dx, dgb[:n].view_as(gamma), dgb[n:].view_as(gamma), None, None
@@ -185,7 +199,7 @@ class _SeqPrologueFn(torch.autograd.Function):
         n, rate, seed = ctx.cfg
         M = x.numel() // n
         dx = torch.empty_like(x)
-        part = torch.empty(ops.layernorm_parts(M) * 3 * n, dtype=torch.float32, device=x.device)
+        part = torch.empty(ops.layernorm_parts(M, n) * 3 * n, dtype=torch.float32, device=x.device)
         if ctx.gdst is not None:            # [gamma | beta | pos] -> the flat gradients
             flat, idx = ctx.gdst
             ops.seq_prologue_bwd(x, pos.contiguous(), g.contiguous(), n, gamma.contiguous(),

@@ -840,7 +840,8 @@ def reduce_adam(part, nparts, n, ld, grad, p, m, v, hyper, beta1=0.9, beta2=0.99
 
 def linear_xent(H, W, bias, labels, eps, ignore, dH, lossv, dW=None, db=None, loss=None,
                 loss_acc=None, step=None):
-    """Fused Linear(16->V) + label-smoothed CrossEntropy, fwd+bwd (no logits).
+    """Fused Linear(E->V) + label-smoothed CrossEntropy, fwd+bwd (no logits);
+    on the GPU E = 16 (MFMA kernels) or 32 / 64 (linear_xent_wide.hip).
     loss (fp32 [1]): mean loss over the non-ignored tokens; loss_acc (fp64
     [1]): += that loss (device running sum). step = (opt, [mW, vW, mb, vb],
     hyper, beta1, beta2, eps, weight_decay): apply the flat optimizer's
@@ -891,24 +892,57 @@ def jagged_ids_to_dense(values, offsets, pad, out):
         ref.jagged_ids_to_dense(values, offsets, pad, out)
 
 
-def attention_fwd(qkv, ids, H, rate, seed, step, pad_id, out):
-    """Fused small-T MHA core: qkv [B,T,3E] fp32 -> out [B,T,E] (key-padding
-    mask from ids != pad_id, hash dropout keyed by (seed, step[0]))."""
+ATTN_SHORT_MAXT = 64       # one wave per (sample, head): csrc/kernels/attention.hip
+ATTN_LONG_MAXT = 512       # tiled kernels with a saved lse: csrc/kernels/attention_long.hip
+ATTN_DK = (4, 8, 16, 32, 64)
+
+
+def _attn_gpu_check(qkv, H, need, have):
+    """Host-side argument checks of the GPU attention core (no kernel is
+    launched on a failure)."""
+    T = qkv.shape[1]
+    dk = qkv.shape[2] // 3 // max(1, int(H))
+    if T > ATTN_LONG_MAXT or dk not in ATTN_DK:
+        raise ValueError(f"attention on the GPU supports T <= {ATTN_LONG_MAXT} and d_k = E / H in "
+                         f"{ATTN_DK}; got T = {T}, d_k = {dk}")
+    if T > ATTN_SHORT_MAXT and any(t is None for t in have):
+        raise ValueError(f"attention: T = {T} > {ATTN_SHORT_MAXT} runs the tiled kernels, which "
+                         f"need {need}")
+
+
+def attention_fwd(qkv, ids, H, rate, seed, step, pad_id, out, lse=None):
+    """Fused MHA core: qkv [B,T,3E] fp32 -> out [B,T,E] (key-padding mask from
+    ids != pad_id, hash dropout keyed by (seed, step[0])). On the GPU T <= 64
+    runs one wave per (sample, head) and ignores ``lse``; 64 < T <= 512 runs
+    the tiled kernels, which write the row log-sum-exp into ``lse``
+    (fp32 [B, H, T], required there) for the backward."""
     if _gpu(qkv):
-        _native().attention_fwd(qkv, ids, int(H), float(rate), int(seed), step, int(pad_id), out)
+        _attn_gpu_check(qkv, H, "lse (fp32 [B, H, T])", (lse,))
+        _native().attention_fwd(qkv, ids, int(H), float(rate), int(seed), step, int(pad_id), out,
+                                lse)
     else:
         ref.attention_fwd(qkv, ids, H, rate, seed, step, pad_id, out)
 
 
-def attention_bwd(qkv, ids, dout, H, rate, seed, step, pad_id, dqkv):
+def attention_bwd(qkv, ids, dout, H, rate, seed, step, pad_id, dqkv, out=None, lse=None):
+    """dqkv of attention_fwd. 64 < T <= 512 on the GPU needs the forward's
+    ``out`` and ``lse``; both are ignored for T <= 64 and on the CPU."""
     if _gpu(qkv):
+        _attn_gpu_check(qkv, H, "the forward's out and lse", (out, lse))
         _native().attention_bwd(qkv, ids, dout, int(H), float(rate), int(seed), step,
-                                int(pad_id), dqkv)
+                                int(pad_id), dqkv, out, lse)
     else:
         ref.attention_bwd(qkv, ids, dout, H, rate, seed, step, pad_id, dqkv)
 
 
-def layernorm_parts(M: int) -> int:
+LN_NARROW_MAXN = 1024      # wider rows (to 32768) take the one-workgroup-per-row path
+
+
+def layernorm_parts(M: int, n: int = 0) -> int:
+    """Row blocks of the LayerNorm backward's partial buffer; 0 for wide rows
+    (n > 1024), whose path does not use ``part``."""
+    if n > LN_NARROW_MAXN:
+        return 0
     return int(_native().layernorm_parts(int(M))) if native_available() else 1
 
 
