@@ -1094,7 +1094,7 @@ def test_load_batch_any_input_dtype_and_offset_views():
 
 @pytest.mark.parametrize("opt", [ops.EMB_ROWWISE_ADAGRAD, ops.EMB_SGD, ops.EMB_ADAGRAD,
                                  ops.EMB_ADAM])
-@pytest.mark.parametrize("D", [32, 128])
+@pytest.mark.parametrize("D", [16, 32, 64, 128, 256, 512])
 def test_embedding_dense_update_matches_reference(opt, D):
     """Replicated tables' step from an all-reduced dense gradient (half the
     rows untouched: they must not move for SGD / Adagrad variants)."""

@@ -107,20 +107,31 @@ def _recv_from(rows, L, B, W, owner, seed, dev):
     return recv.view(-1).to(dev), meta.to(dev), cap, total
 
 
-@pytest.mark.parametrize("W", [1, 4])
-@pytest.mark.parametrize("out_dtype", [torch.bfloat16, torch.float32])
-@pytest.mark.parametrize("rows,L,B,D", [([5000, 300], [1, 4], 128, 128), ([777] * 3, [2, 1, 9], 64, 64)])
-def test_rw_pool_matches_reference(W, out_dtype, rows, L, B, D):
+def _check_rw_pool(W, out_dtype, rows, L, B, D, mean):
     recv, meta, cap, total = _recv_from(rows, L, B, W, owner=W - 1, seed=3, dev=DEV)
     nrw = len(rows)
     Wt = torch.randn(total + 1, D, device=DEV)
     starts = torch.zeros(W * (nrw * B + 1), dtype=torch.int32, device=DEV)
     out = torch.full((W * B * nrw * D,), 5.0, dtype=out_dtype, device=DEV)
-    ops.rw_pool(Wt, recv, meta, nrw, W, B, cap, False, starts, out, nrw * D)
+    ops.rw_pool(Wt, recv, meta, nrw, W, B, cap, mean, starts, out, nrw * D)
     exp = torch.zeros(W * B * nrw * D, dtype=torch.float32)
-    ref.rw_pool(Wt.cpu(), recv.cpu(), meta.cpu(), nrw, W, B, cap, False, exp, nrw * D)
+    ref.rw_pool(Wt.cpu(), recv.cpu(), meta.cpu(), nrw, W, B, cap, mean, exp, nrw * D)
     tol = 2e-2 if out_dtype == torch.bfloat16 else 1e-5
     assert torch.allclose(out.float().cpu(), exp, atol=tol, rtol=tol)
+
+
+@pytest.mark.parametrize("W", [1, 4])
+@pytest.mark.parametrize("out_dtype", [torch.bfloat16, torch.float32])
+@pytest.mark.parametrize("rows,L,B,D", [([5000, 300], [1, 4], 128, 128), ([777] * 3, [2, 1, 9], 64, 64),
+                                        ([5000, 300], [1, 4], 128, 16), ([777] * 3, [2, 1, 9], 64, 256),
+                                        ([5000, 300], [1, 4], 128, 32)])
+def test_rw_pool_matches_reference(W, out_dtype, rows, L, B, D):
+    _check_rw_pool(W, out_dtype, rows, L, B, D, False)
+
+
+def test_rw_pool_mean_matches_reference():
+    """mean pooling (every row scaled by 1 / L[j]) at the widest rows."""
+    _check_rw_pool(4, torch.float32, [777] * 3, [2, 1, 9], 64, 256, True)
 
 
 @pytest.mark.parametrize("opt", [ops.EMB_ROWWISE_ADAGRAD, ops.EMB_SGD, ops.EMB_ADAM])
