@@ -95,6 +95,11 @@ void gemm(const Tensor& a_in, bool a_col, const Tensor& b_in, bool b_col,
   if (a_col) TORCH_CHECK(M % 8 == 0 && M >= 8, "gemm: col-layout A needs M % 8 == 0");
   if (b_col) TORCH_CHECK(N % 8 == 0 && N >= 8, "gemm: col-layout B needs N % 8 == 0");
   TORCH_CHECK(splits >= 1 && splits <= K / 64, "gemm: bad split count");
+  // every slab would get the whole epilogue: splits x bias in the slab sum,
+  // ReLU / mask on partial sums
+  TORCH_CHECK(splits == 1 || !(bias || relu || mask),
+              "gemm: splits > 1 takes no bias, relu or mask (the epilogue would act on every "
+              "partial sum)");
   tdfo::GemmArgs g{};
   g.A = bf16_ptr(a); g.lda = a.stride(0); g.a_col = a_col;
   g.B = bf16_ptr(b); g.ldb = b.stride(0); g.b_col = b_col;

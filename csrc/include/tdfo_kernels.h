@@ -14,7 +14,9 @@ namespace tdfo {
 //   b_col == 0: B stored [N][K] (i.e. torch Linear weight layout)
 //   b_col == 1: B stored [K][N]
 // Epilogue (in order): +bias[n] (fp32), relu, *= (mask[m,n] > 0), then store
-// bf16 C and/or fp32 C32 (C32 + z*M*ldc32 for split-K slice z).
+// bf16 C and/or fp32 C32 (C32 + z*M*ldc32 for split-K slice z). The kernels
+// run the epilogue on every slice, so splits > 1 goes with no bias, relu or
+// mask (the binding refuses the combination).
 struct GemmArgs {
   const uint16_t* A; int64_t lda; int a_col;
   const uint16_t* B; int64_t ldb; int b_col;

@@ -42,7 +42,8 @@ def gemm(a, a_col, b, b_col, bias=None, relu=False, mask=None, out=None, out32=N
          mul=None, add=None, out2=None, ldc32=0, csum_col=-1):
     """C = A B (+ epilogue). out32: fp32 split-K slabs [splits][M][ldc32]
     (ldc32 0 = N); csum_col >= 0 (col-layout A): each slab's column csum_col
-    also gets the sum over that split's K range of A's column m."""
+    also gets the sum over that split's K range of A's column m. splits > 1
+    takes no bias, relu or mask (refused on both devices)."""
     if _gpu(a):
         _native().gemm(a, a_col, b, b_col, bias, relu, mask, out, out32, splits, mul, add, out2,
                        ldc32, csum_col)

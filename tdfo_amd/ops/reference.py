@@ -21,6 +21,10 @@ def _f(t: torch.Tensor) -> torch.Tensor:
 
 def gemm(a, a_col, b, b_col, bias=None, relu=False, mask=None, out=None, out32=None, splits=1,
          mul=None, add=None, out2=None, ldc32=0, csum_col=-1):
+    if splits > 1 and (bias is not None or relu or mask is not None):
+        # same refusal and message as the native binding
+        raise RuntimeError("gemm: splits > 1 takes no bias, relu or mask (the epilogue would act "
+                           "on every partial sum)")
     A = _f(a).t() if a_col else _f(a)          # [M, K]
     Bm = _f(b) if b_col else _f(b).t()         # [K, N]
     c = A @ Bm
