@@ -830,14 +830,24 @@ void check_i64(const Tensor& t, const char* n) {
   TORCH_CHECK(t.scalar_type() == at::kLong && t.is_contiguous(), n, " must be contiguous int64");
 }
 
+// bf16 table rows: the widths the bf16 kernels are built for
+void check_bf16_table(bool wb, int64_t D) {
+  TORCH_CHECK(!wb || D == 64 || D == 128 || D == 256,
+              "bf16 embedding tables support D in {64, 128, 256}, got D = ", D,
+              " (fp32 tables: {16, 32, 64, 128, 256, 512})");
+}
+
 void embedding_bag_fwd(const Tensor& W, const Tensor& row_offset, const Tensor& indices,
                        const Tensor& offsets, const Tensor& out_off,
                        const c10::optional<Tensor>& psw, int64_t T, int64_t B, bool mean,
                        const Tensor& out, int64_t out_stride, bool onehot, at::TensorList bumps) {
   check_dev(W, "W"); check_2d_rowmajor(W, "W");
-  TORCH_CHECK(W.scalar_type() == at::kFloat && W.is_contiguous(), "W must be contiguous fp32");
+  const bool wb = W.scalar_type() == at::kBFloat16;
+  TORCH_CHECK((W.scalar_type() == at::kFloat || wb) && W.is_contiguous(),
+              "W must be contiguous fp32 or bf16");
   const int64_t D = W.size(1);
   TORCH_CHECK(D == 16 || D == 32 || D == 64 || D == 128 || D == 256 || D == 512, "embedding D unsupported");
+  check_bf16_table(wb, D);
   check_i64(row_offset, "row_offset"); check_i64(indices, "indices");
   check_i64(offsets, "offsets"); check_i64(out_off, "out_off");
   TORCH_CHECK(row_offset.numel() == T && out_off.numel() == T && offsets.numel() == T * B + 1,
@@ -846,7 +856,7 @@ void embedding_bag_fwd(const Tensor& W, const Tensor& row_offset, const Tensor& 
   TORCH_CHECK(out.scalar_type() == at::kBFloat16 || out.scalar_type() == at::kFloat, "out dtype");
   TORCH_CHECK(out_stride % 4 == 0, "out_stride must be a multiple of 4");
   tdfo::EmbFwdArgs a{};
-  a.W = W.data_ptr<float>(); a.D = (int)D;
+  a.W = (const float*)W.data_ptr(); a.D = (int)D; a.w_bf16 = wb;
   a.row_offset = row_offset.data_ptr<int64_t>(); a.indices = indices.data_ptr<int64_t>();
   a.offsets = offsets.data_ptr<int64_t>(); a.out_off = out_off.data_ptr<int64_t>();
   if (psw) {
@@ -871,11 +881,24 @@ void embedding_bag_fwd(const Tensor& W, const Tensor& row_offset, const Tensor& 
 tdfo::EmbBwdArgs emb_bwd_args(const Tensor& W, const Tensor& row_offset, const Tensor& indices,
                               const Tensor& offsets, const Tensor& grad_off,
                               const c10::optional<Tensor>& psw, int64_t T, int64_t B, bool mean,
-                              int64_t key_bits, int64_t grad_stride, int64_t segsort) {
+                              int64_t key_bits, int64_t grad_stride, int64_t segsort,
+                              int64_t sr_seed = 0,
+                              const c10::optional<Tensor>& sr_counter = c10::nullopt,
+                              bool sr = false) {
   check_dev(W, "W");
-  TORCH_CHECK(W.scalar_type() == at::kFloat && W.is_contiguous() && W.dim() == 2, "W fp32 2-D");
+  const bool wb = W.scalar_type() == at::kBFloat16;
+  TORCH_CHECK((W.scalar_type() == at::kFloat || wb) && W.is_contiguous() && W.dim() == 2,
+              "W fp32 or bf16 2-D");
   const int64_t D = W.size(1);
   TORCH_CHECK(D == 16 || D == 32 || D == 64 || D == 128 || D == 256 || D == 512, "embedding D unsupported");
+  check_bf16_table(wb, D);
+  TORCH_CHECK(!(wb && sr) || sr_counter,
+              "bf16 table with stochastic rounding needs the store's counter (sr_counter)");
+  if (sr_counter) {
+    check_dev(*sr_counter, "sr_counter");
+    TORCH_CHECK(sr_counter->scalar_type() == at::kLong && sr_counter->numel() == 1,
+                "sr_counter: int64 device scalar");
+  }
   check_i64(row_offset, "row_offset"); check_i64(indices, "indices");
   check_i64(offsets, "offsets"); check_i64(grad_off, "grad_off");
   TORCH_CHECK(offsets.numel() == T * B + 1 && grad_off.numel() == T && row_offset.numel() == T, "bwd counts");
@@ -883,7 +906,13 @@ tdfo::EmbBwdArgs emb_bwd_args(const Tensor& W, const Tensor& row_offset, const T
   const int64_t nnz = indices.numel();
   TORCH_CHECK(nnz < (1LL << 31), "nnz too large");
   tdfo::EmbBwdArgs a{};
-  a.W = W.data_ptr<float>(); a.D = (int)D;
+  a.W = (float*)W.data_ptr(); a.D = (int)D;
+  if (wb) {                      // (fp32 tables ignore the rounding arguments)
+    a.w_bf16 = 1;
+    a.sr = sr;
+    a.sr_seed = (uint32_t)sr_seed;
+    if (sr_counter) a.sr_counter = sr_counter->data_ptr<int64_t>();
+  }
   a.row_offset = row_offset.data_ptr<int64_t>(); a.indices = indices.data_ptr<int64_t>();
   a.offsets = offsets.data_ptr<int64_t>(); a.grad_off = grad_off.data_ptr<int64_t>();
   if (psw) a.psw = psw->data_ptr<float>();
@@ -904,6 +933,9 @@ void emb_bwd_opt_args(tdfo::EmbBwdArgs& a, const Tensor& W, const Tensor& grad, 
   TORCH_CHECK(hyper.scalar_type() == at::kFloat && hyper.numel() >= 2 && hyper.is_cuda(), "hyper fp32[>=2] on device");
   a.grad = grad.data_ptr(); a.grad_bf16 = grad.scalar_type() == at::kBFloat16;
   a.opt = (int)opt;
+  TORCH_CHECK(!a.w_bf16 || opt == tdfo::EMB_SGD || opt == tdfo::EMB_ROWWISE_ADAGRAD,
+              "bf16 embedding tables support EMB_SGD and EMB_ROWWISE_ADAGRAD only (Adagrad, Adam "
+              "and the dense-gradient mode keep fp32 state per element: use an fp32 table)");
   const int64_t rows = W.size(0);
   if (opt == tdfo::EMB_ROWWISE_ADAGRAD) {
     TORCH_CHECK(state1 && state1->numel() == rows && state1->scalar_type() == at::kFloat, "rowwise state [rows]");
@@ -943,9 +975,10 @@ void embedding_bwd(const Tensor& W, const Tensor& row_offset, const Tensor& indi
                    int64_t key_bits, const Tensor& grad, int64_t grad_stride, int64_t opt,
                    const c10::optional<Tensor>& state1, const c10::optional<Tensor>& state2,
                    const Tensor& hyper, double eps, double beta1, double beta2,
-                   double weight_decay, const c10::optional<Tensor>& dense_grad, int64_t segsort) {
+                   double weight_decay, const c10::optional<Tensor>& dense_grad, int64_t segsort,
+                   int64_t sr_seed, const c10::optional<Tensor>& sr_counter, bool sr) {
   auto a = emb_bwd_args(W, row_offset, indices, offsets, grad_off, psw, T, B, mean, key_bits,
-                        grad_stride, segsort);
+                        grad_stride, segsort, sr_seed, sr_counter, sr);
   emb_bwd_opt_args(a, W, grad, opt, state1, state2, hyper, eps, beta1, beta2, weight_decay,
                    dense_grad);
   const size_t ws = tdfo::embedding_bwd_workspace(a.nnz, a.D);
@@ -968,9 +1001,10 @@ void embedding_bwd_prepare(const Tensor& W, const Tensor& row_offset, const Tens
                            const Tensor& offsets, const Tensor& grad_off,
                            const c10::optional<Tensor>& psw, int64_t T, int64_t B, bool mean,
                            int64_t key_bits, int64_t grad_stride, int64_t segsort,
-                           const Tensor& work, const c10::optional<Tensor>& bag_len) {
+                           const Tensor& work, const c10::optional<Tensor>& bag_len,
+                           const c10::optional<Tensor>& sr_counter) {
   auto a = emb_bwd_args(W, row_offset, indices, offsets, grad_off, psw, T, B, mean, key_bits,
-                        grad_stride, segsort);
+                        grad_stride, segsort, 0, sr_counter, false);
   set_emb_ws(a, work);
   if (bag_len) {
     check_dev(*bag_len, "bag_len");
@@ -988,9 +1022,10 @@ void embedding_bwd_apply(const Tensor& W, const Tensor& row_offset, const Tensor
                          const c10::optional<Tensor>& state1, const c10::optional<Tensor>& state2,
                          const Tensor& hyper, double eps, double beta1, double beta2,
                          double weight_decay, const c10::optional<Tensor>& dense_grad,
-                         int64_t segsort, const Tensor& work) {
+                         int64_t segsort, const Tensor& work, int64_t sr_seed,
+                         const c10::optional<Tensor>& sr_counter, bool sr) {
   auto a = emb_bwd_args(W, row_offset, indices, offsets, grad_off, psw, T, B, mean, key_bits,
-                        grad_stride, segsort);
+                        grad_stride, segsort, sr_seed, sr_counter, sr);
   emb_bwd_opt_args(a, W, grad, opt, state1, state2, hyper, eps, beta1, beta2, weight_decay,
                    dense_grad);
   set_emb_ws(a, work);
@@ -1002,7 +1037,9 @@ void embedding_dense_update(const Tensor& W, const Tensor& grad, int64_t rows, i
                             const Tensor& hyper, double eps, double beta1, double beta2,
                             double weight_decay, bool clear_grad) {
   check_dev(W, "W");
-  TORCH_CHECK(W.scalar_type() == at::kFloat && W.is_contiguous() && W.dim() == 2, "W fp32 2-D");
+  TORCH_CHECK(W.scalar_type() == at::kFloat && W.is_contiguous() && W.dim() == 2,
+              "embedding_dense_update: W must be fp32 2-D (bf16 tables take the sparse "
+              "embedding_bwd with SGD or row-wise Adagrad only)");
   const int64_t D = W.size(1);
   TORCH_CHECK(D == 16 || D == 32 || D == 64 || D == 128 || D == 256 || D == 512, "embedding D unsupported");
   TORCH_CHECK(rows >= 0 && rows <= W.size(0), "rows out of range");
@@ -1190,7 +1227,8 @@ void rw_grads_gather(const Tensor& map, int64_t W, int64_t cap, int64_t D, const
 tdfo::EmbBwdArgs emb_rw_args(const Tensor& W, int64_t Wsz, int64_t B, int64_t cap, bool mean,
                              int64_t key_bits) {
   check_dev(W, "W");
-  TORCH_CHECK(W.scalar_type() == at::kFloat && W.is_contiguous() && W.dim() == 2, "W fp32 2-D");
+  TORCH_CHECK(W.scalar_type() == at::kFloat && W.is_contiguous() && W.dim() == 2,
+              "row-wise shards: W must be fp32 2-D (bf16 tables are table-wise / column-wise only)");
   const int64_t D = W.size(1);
   TORCH_CHECK(D == 16 || D == 32 || D == 64 || D == 128 || D == 256 || D == 512, "embedding D unsupported");
   TORCH_CHECK(key_bits >= 1 && key_bits <= 64, "key_bits");
@@ -1272,6 +1310,20 @@ void check_finite(const Tensor& g, const Tensor& found) {
   check_dev(g, "g");
   TORCH_CHECK(g.scalar_type() == at::kFloat && g.is_contiguous(), "g fp32");
   tdfo::check_finite(g.data_ptr<float>(), g.numel(), found.data_ptr<float>(), cur_stream());
+}
+
+void bf16_stochastic_round(const Tensor& x, int64_t seed, const Tensor& counter, int64_t row0,
+                           const Tensor& out) {
+  check_dev(x, "x"); check_dev(out, "out"); check_dev(counter, "counter");
+  TORCH_CHECK(x.dim() == 2 && x.scalar_type() == at::kFloat && x.is_contiguous(),
+              "bf16_stochastic_round: x contiguous fp32 [n, D]");
+  TORCH_CHECK(out.scalar_type() == at::kBFloat16 && out.is_contiguous() &&
+              out.numel() == x.numel(), "bf16_stochastic_round: out contiguous bf16 of x's size");
+  TORCH_CHECK(counter.scalar_type() == at::kLong && counter.numel() == 1,
+              "bf16_stochastic_round: counter int64 device scalar");
+  TORCH_CHECK(row0 >= 0, "bf16_stochastic_round: row0 >= 0");
+  tdfo::bf16_stochastic_round(x.data_ptr<float>(), bf16_mut(out), x.numel(), (int)x.size(1),
+                              (uint32_t)seed, counter.data_ptr<int64_t>(), row0, cur_stream());
 }
 
 void cast_bf16(const Tensor& x, const Tensor& y) {
@@ -1885,18 +1937,20 @@ TORCH_LIBRARY(tdfo, m) {
   m.def("embedding_bwd(Tensor(a!) W, Tensor row_offset, Tensor indices, Tensor offsets, Tensor grad_off, "
         "Tensor? psw, int T, int B, bool mean, int key_bits, Tensor grad, int grad_stride, int opt, "
         "Tensor(b!)? state1, Tensor(c!)? state2, Tensor hyper, float eps, float beta1, float beta2, "
-        "float weight_decay, Tensor(d!)? dense_grad, int segsort) -> ()");
+        "float weight_decay, Tensor(d!)? dense_grad, int segsort, int sr_seed=0, "
+        "Tensor(e!)? sr_counter=None, bool sr=False) -> ()");
   m.def("embedding_bwd_workspace(int nnz, int D) -> int", [](int64_t nnz, int64_t D) {
     return (int64_t)tdfo::embedding_bwd_workspace(nnz < 1 ? 1 : nnz, (int)D);
   });
   m.def("embedding_bwd_prepare(Tensor W, Tensor row_offset, Tensor indices, Tensor offsets, "
         "Tensor grad_off, Tensor? psw, int T, int B, bool mean, int key_bits, int grad_stride, "
-        "int segsort, Tensor(a!) workspace, Tensor? bag_len=None) -> ()");
+        "int segsort, Tensor(a!) workspace, Tensor? bag_len=None, Tensor(b!)? sr_counter=None) -> ()");
   m.def("embedding_bwd_apply(Tensor(a!) W, Tensor row_offset, Tensor indices, Tensor offsets, "
         "Tensor grad_off, Tensor? psw, int T, int B, bool mean, int key_bits, Tensor grad, "
         "int grad_stride, int opt, Tensor(b!)? state1, Tensor(c!)? state2, Tensor hyper, "
         "float eps, float beta1, float beta2, float weight_decay, Tensor(d!)? dense_grad, "
-        "int segsort, Tensor(e!) workspace) -> ()");
+        "int segsort, Tensor(e!) workspace, int sr_seed=0, Tensor? sr_counter=None, "
+        "bool sr=False) -> ()");
   m.def("embedding_dense_update(Tensor(a!) W, Tensor(d!) grad, int rows, int opt, Tensor(b!)? state1, "
         "Tensor(c!)? state2, Tensor hyper, float eps, float beta1, float beta2, "
         "float weight_decay, bool clear_grad) -> ()");
@@ -1925,6 +1979,7 @@ TORCH_LIBRARY(tdfo, m) {
   m.def("check_finite(Tensor g, Tensor(a!) found) -> ()");
   m.def("sort_pairs(Tensor keys, Tensor vals, int key_bits) -> (Tensor, Tensor)");
   m.def("cast_bf16(Tensor x, Tensor(a!) y) -> ()");
+  m.def("bf16_stochastic_round(Tensor x, int seed, Tensor counter, int row0, Tensor(a!) out) -> ()");
   m.def("synth_criteo(int seed, int rank, int batch_index, int B, Tensor rows, Tensor pooling, "
         "Tensor base, int dist, float alpha, Tensor w_dense, Tensor table_bias, Tensor(a!) dense, "
         "Tensor(b!) ids, Tensor(c!) label) -> ()");
@@ -1999,6 +2054,7 @@ TORCH_LIBRARY_IMPL(tdfo, CUDA, m) {
   m.impl("check_finite", check_finite);
   m.impl("sort_pairs", sort_pairs);
   m.impl("cast_bf16", cast_bf16);
+  m.impl("bf16_stochastic_round", bf16_stochastic_round);
   m.impl("slab_reduce", slab_reduce);
   m.impl("synth_ids", synth_ids);
   m.impl("synth_dense", synth_dense);

@@ -37,6 +37,35 @@ __device__ __forceinline__ uint32_t pack2bf(float a, float b) {
   return (uint32_t)f2bf(a) | ((uint32_t)f2bf(b) << 16);
 }
 
+// Counter hash shared with the dropout kernels (attention.hip's hash3;
+// tdfo_amd.ops.reference._hash3 is its Python mirror).
+__device__ __forceinline__ uint32_t sr_hash3(uint32_t a, uint32_t b, uint32_t c) {
+  uint32_t h = a * 0x9E3779B1u ^ (b + 0x7F4A7C15u) * 0x85EBCA77u ^ (c + 0x165667B1u) * 0xC2B2AE3Du;
+  h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
+  return h;
+}
+
+// 64-bit row index -> the hash's 32-bit row word (the identity below 2^32)
+__device__ __forceinline__ uint32_t fold32(uint64_t row) {
+  return (uint32_t)row ^ ((uint32_t)(row >> 32) * 0x9E3779B1u);
+}
+
+// key of one update's random stream: seed and the store's update counter
+__device__ __forceinline__ uint32_t sr_key(uint32_t seed, uint32_t counter) {
+  return seed ^ (counter * 0x632BE5ABu);
+}
+
+// Stochastic rounding f32 -> bf16: 16 random bits, a pure function of
+// (key, row, column), are added below the kept half, so a finite x goes to
+// the bf16 neighbour away from zero with probability (low 16 bits) / 65536
+// and a bf16 value never moves. NaN and +-inf take the nearest-even cast.
+__device__ __forceinline__ uint16_t f2bf_sr(float x, uint32_t key, uint32_t rowh, uint32_t col) {
+  const uint32_t bits = __float_as_uint(x);
+  if ((bits & 0x7f800000u) == 0x7f800000u) return f2bf(x);
+  const uint32_t r = sr_hash3(key, rowh, col) & 0xffffu;
+  return (uint16_t)((bits + r) >> 16);
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

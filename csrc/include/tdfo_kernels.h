@@ -119,6 +119,7 @@ struct BumpArgs {
 
 struct EmbFwdArgs {
   const float* W; int D;
+  int w_bf16 = 0;              // table elements are bf16 (W then points at uint16 storage)
   const int64_t* row_offset;   // [T] (device)
   const int64_t* indices;      // [nnz] (device)
   const int64_t* offsets;      // [T*B+1] (device)
@@ -220,6 +221,17 @@ struct EmbBwdArgs {
   TwoTowerArgs tower{};
   int tower_on = 0;
   int side_block0 = 0;         // internal: first side block of the update launch
+  // bf16 table rows (W then points at uint16 storage; SGD and row-wise Adagrad,
+  // D = 64 / 128 / 256): the update runs in fp32 on the widened row and only
+  // the row store rounds -- to nearest even, or (sr) stochastically with
+  // r = hash3(sr_seed ^ (counter * 0x632BE5AB), fold32(row), column) & 0xFFFF,
+  // stored = (bits + r) >> 16. sr_counter (device int64, owned by the store)
+  // is advanced once by thread 0 of block 0 of the ids half's first launch
+  // and read by the update launches.
+  int w_bf16 = 0;
+  int sr = 0;
+  uint32_t sr_seed = 0;
+  int64_t* sr_counter = nullptr;
 };
 size_t embedding_bwd_workspace(int64_t nnz, int D);
 // One-hot batches (nnz == T*B, B <= 8192): per-table LDS sort in one launch
@@ -359,6 +371,11 @@ void dense_optimizer(const DenseOptArgs& a, hipStream_t s);
 // found_inf[0] = any(!isfinite(g)) over n (caller zeroes it first).
 void check_finite(const float* g, int64_t n, float* found_inf, hipStream_t s);
 void cast_f32_bf16(const float* x, uint16_t* y, int64_t n, hipStream_t s);
+// y[n] (bf16 bits) = x[n] stochastically rounded as the bf16 embedding tables'
+// row store does (EmbBwdArgs::sr), element i keyed by (row0 + i / D, i % D);
+// counter: device int64 scalar, read only.
+void bf16_stochastic_round(const float* x, uint16_t* y, int64_t n, int D, uint32_t seed,
+                           const int64_t* counter, int64_t row0, hipStream_t s);
 // Batch inputs in one launch: ids copy, label copy, dense fp32 -> bf16 x0[:, :nd].
 void batch_load(const float* dense, int nd, int64_t ld_dense, uint16_t* x0, int64_t ldx,
                 const int64_t* ids, int64_t* ids_dst, int64_t n, const float* label,

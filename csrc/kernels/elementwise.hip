@@ -359,4 +359,30 @@ void batch_load(const float* dense, int nd, int64_t ld_dense, uint16_t* x0, int6
   TDFO_CHECK_HIP(hipGetLastError());
 }
 
+// y[i, c] = f2bf_sr(x[i, c]) keyed by (row0 + i, c): the bf16 tables' row
+// store (embedding.hip) as an op of its own -- converts an fp32 table into a
+// bf16 store, and lets the rounding be checked against its Python mirror.
+__global__ __launch_bounds__(256) void bf16_sr_kernel(const float* __restrict__ x,
+                                                      uint16_t* __restrict__ y, int64_t n, int D,
+                                                      uint32_t seed,
+                                                      const int64_t* __restrict__ counter,
+                                                      int64_t row0) {
+  const uint32_t key = sr_key(seed, (uint32_t)*counter);
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / D;
+    y[i] = f2bf_sr(x[i], key, fold32((uint64_t)(row0 + r)), (uint32_t)(i - r * D));
+  }
+}
+
+void bf16_stochastic_round(const float* x, uint16_t* y, int64_t n, int D, uint32_t seed,
+                           const int64_t* counter, int64_t row0, hipStream_t s) {
+  if (n <= 0) return;
+  int64_t blocks = (n + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(bf16_sr_kernel, dim3(blocks), dim3(256), 0, s, x, y, n, D, seed, counter,
+                     row0);
+  TDFO_CHECK_HIP(hipGetLastError());
+}
+
 }  // namespace tdfo

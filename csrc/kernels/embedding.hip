@@ -9,6 +9,13 @@
 // (out + b*out_stride + out_off[t]), e.g. the interaction input or the
 // all-to-all send buffer, so no concat/permute pass follows.
 //
+// Table rows are fp32 or bf16 (EmbFwdArgs / EmbBwdArgs::w_bf16; D = 64 / 128 /
+// 256, SGD and row-wise Adagrad). bf16 rows keep every lane mapping (8-B row
+// loads in the forward: the D/8-lane, 16-B form measured within 1 %,
+// profiles/bf16_tables.md), are widened to fp32 where they are used, and
+// only the update's row store rounds -- to nearest even or stochastically
+// (f2bf_sr, tdfo_common.h). The fp32 instantiations are the code they were.
+//
 // Backward + optimizer, with no float atomics (atomics run at ~1.3 TB/s on
 // MI355X and are order-dependent) and load-balanced under skew
 // (cdna_hip_programming.md Appendix B "Scatter / gather / embedding"):
@@ -44,7 +51,36 @@ __device__ __forceinline__ void fwd_bumps(const EmbFwdArgs& a) {
   }
 }
 
-template <int D, bool OUT_BF16>
+// Table rows in fp32 or (WB) bf16. A bf16 row keeps the fp32 lane mapping:
+// D/4 lanes per bag, each lane's four elements one 8-B load widened to fp32
+// on arrival (a 16-bit shift), so the accumulation, the pooling and the
+// output stores -- whose offsets are multiples of 4 elements, not 8 -- are
+// the fp32 path's.
+template <bool WB>
+__device__ __forceinline__ const float* row_base(const float* W, int64_t elem) {
+  if constexpr (WB) return (const float*)((const uint16_t*)W + elem);
+  else return W + elem;
+}
+// a lane's four row elements as loaded (bf16: packed, half the registers of
+// the rows kept in flight) and widened to fp32 where they are used
+template <bool WB>
+using Row4 = typename std::conditional<WB, uint2, float4>::type;
+template <bool WB>
+__device__ __forceinline__ Row4<WB> ld_row4_raw(const float* base, int64_t elem) {
+  if constexpr (WB) return *(const uint2*)((const uint16_t*)base + elem);
+  else return *(const float4*)(base + elem);
+}
+__device__ __forceinline__ float4 widen4(const float4& v) { return v; }
+__device__ __forceinline__ float4 widen4(const uint2& v) {
+  return make_float4(__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u),
+                     __uint_as_float(v.y << 16), __uint_as_float(v.y & 0xffff0000u));
+}
+template <bool WB>
+__device__ __forceinline__ float4 ld_row4(const float* base, int64_t elem) {
+  return widen4(ld_row4_raw<WB>(base, elem));
+}
+
+template <int D, bool OUT_BF16, bool WB = false>
 __global__ __launch_bounds__(256) void emb_fwd_onehot_kernel(EmbFwdArgs a) {
   fwd_bumps(a);
   constexpr int LPB = (D / 4) < 64 ? (D / 4) : 64;  // lanes per bag
@@ -59,11 +95,11 @@ __global__ __launch_bounds__(256) void emb_fwd_onehot_kernel(EmbFwdArgs a) {
     const bool has1 = j1 < nbags;
     const int t0 = (int)(j0 / a.B), t1 = has1 ? (int)(j1 / a.B) : t0;
     const int64_t id0 = a.indices[j0], id1 = has1 ? a.indices[j1] : id0;
-    const float* r0 = a.W + (a.row_offset[t0] + id0) * D;
-    const float* r1 = a.W + (a.row_offset[t1] + id1) * D;
+    const float* r0 = row_base<WB>(a.W, (a.row_offset[t0] + id0) * D);
+    const float* r1 = row_base<WB>(a.W, (a.row_offset[t1] + id1) * D);
     for (int c = sl * 4; c < D; c += LPB * 4) {
-      const float4 v0 = *(const float4*)(r0 + c);
-      const float4 v1 = *(const float4*)(r1 + c);
+      const float4 v0 = ld_row4<WB>(r0, c);
+      const float4 v1 = ld_row4<WB>(r1, c);
       const float w0 = a.psw ? a.psw[j0] : 1.f, w1 = a.psw ? a.psw[j1 < nbags ? j1 : j0] : 1.f;
       const float4 o0 = make_float4(v0.x * w0, v0.y * w0, v0.z * w0, v0.w * w0);
       const float4 o1 = make_float4(v1.x * w1, v1.y * w1, v1.z * w1, v1.w * w1);
@@ -97,7 +133,7 @@ __device__ __forceinline__ void emb_wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <int D, bool OUT_BF16, int RIF>
+template <int D, bool OUT_BF16, int RIF, bool WB = false>
 __global__ __launch_bounds__(256) void emb_fwd_kernel(EmbFwdArgs a) {
   fwd_bumps(a);
   constexpr int LPB = (D / 4) < 64 ? (D / 4) : 64;  // lanes per bag
@@ -137,7 +173,7 @@ __global__ __launch_bounds__(256) void emb_fwd_kernel(EmbFwdArgs a) {
     int nch = (len + CH - 1) / CH;
 #pragma unroll
     for (int o = LPB; o < 64; o <<= 1) nch = max(nch, __shfl_xor(nch, o));
-    const float* wbase = a.W + (active ? a.row_offset[t] : 0) * D;
+    const float* wbase = row_base<WB>(a.W, (active ? a.row_offset[t] : 0) * D);
     float4 acc[NCP];
 #pragma unroll
     for (int cp = 0; cp < NCP; ++cp) acc[cp] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -169,7 +205,7 @@ __global__ __launch_bounds__(256) void emb_fwd_kernel(EmbFwdArgs a) {
 #pragma unroll
       for (int o = LPB; o < 64; o <<= 1) nmax = max(nmax, __shfl_xor(nmax, o));
       for (int u0 = 0; u0 < nmax; u0 += RIF) {
-        float4 r[RIF][NCP];
+        Row4<WB> r[RIF][NCP];
         float wt[RIF];
 #pragma unroll
         for (int v = 0; v < RIF; ++v) {
@@ -178,15 +214,24 @@ __global__ __launch_bounds__(256) void emb_fwd_kernel(EmbFwdArgs a) {
           wt[v] = ok ? wts[u0 + v] : 0.f;
 #pragma unroll
           for (int cp = 0; cp < NCP; ++cp)
-            r[v][cp] = ok ? *(const float4*)(wbase + row * D + (cp * LPB + sl) * 4)
-                          : make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (WB)
+              r[v][cp] = ok ? ld_row4_raw<WB>(wbase, row * D + (cp * LPB + sl) * 4) : make_uint2(0, 0);
+            else
+              r[v][cp] = ok ? *(const float4*)(wbase + row * D + (cp * LPB + sl) * 4)
+                            : make_float4(0.f, 0.f, 0.f, 0.f);
         }
 #pragma unroll
         for (int v = 0; v < RIF; ++v)
 #pragma unroll
           for (int cp = 0; cp < NCP; ++cp) {
-            acc[cp].x += wt[v] * r[v][cp].x; acc[cp].y += wt[v] * r[v][cp].y;
-            acc[cp].z += wt[v] * r[v][cp].z; acc[cp].w += wt[v] * r[v][cp].w;
+            if constexpr (WB) {
+              const float4 x = widen4(r[v][cp]);
+              acc[cp].x += wt[v] * x.x; acc[cp].y += wt[v] * x.y;
+              acc[cp].z += wt[v] * x.z; acc[cp].w += wt[v] * x.w;
+            } else {
+              acc[cp].x += wt[v] * r[v][cp].x; acc[cp].y += wt[v] * r[v][cp].y;
+              acc[cp].z += wt[v] * r[v][cp].z; acc[cp].w += wt[v] * r[v][cp].w;
+            }
           }
       }
     }
@@ -234,6 +279,7 @@ __global__ __launch_bounds__(256) void emb_keys_kernel(const EmbBwdArgs a, K* __
   if (blockIdx.x == 0 && threadIdx.x == 0) {  // read by later kernels
     tail_count[0] = 0;
     tail_count[1] = 0;
+    if (a.sr_counter) *a.sr_counter += 1;     // bf16 tables: this update's rounding stream
   }
   const int64_t nbags = (int64_t)a.T * a.B;
   // fixed bag lengths: the virtual tables' first positions in LDS, a
@@ -448,6 +494,7 @@ __device__ __forceinline__ void segsort_table(
   if (t == 0 && tid == 0) {                         // read by later kernels
     tail_count[0] = 0;
     tail_count[1] = 0;
+    if (a.sr_counter) *a.sr_counter += 1;
   }
   const int n = a.B;
   const int64_t s0 = (int64_t)t * a.B;
@@ -583,6 +630,7 @@ __global__ __launch_bounds__(SEG_THREADS) void emb_segsort_split_kernel(
   if (blockIdx.x == 0 && tid == 0) {              // read by later kernels
     tail_count[0] = 0;
     tail_count[1] = 0;
+    if (a.sr_counter) *a.sr_counter += 1;
   }
   const int n = a.B;
   const int64_t s0 = (int64_t)t * a.B;
@@ -807,6 +855,76 @@ __device__ __forceinline__ void load_row(float (&wv)[BwdCfg<D>::EPL], const floa
   }
 }
 
+// bf16 table rows (WB): a lane's slice stays packed bits until it is used (as
+// GradRaw below: the chunk kernel holds CH of them per lane), one 2 / 4 / 8 /
+// 16-B access per lane for 1 / 2 / 4 / 8 elements.
+typedef __attribute__((ext_vector_type(2))) uint32_t u32x2_t;
+typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;
+template <int D>
+struct RowBits {
+  uint16_t v[BwdCfg<D>::EPL];
+};
+
+template <int D, bool NT = false>
+__device__ __forceinline__ void load_row_bits(RowBits<D>& r, const uint16_t* w) {
+  constexpr int EPL = BwdCfg<D>::EPL;
+  if constexpr (EPL == 2) {
+    const uint32_t v = row_ld<NT>((const uint32_t*)w);
+    r.v[0] = (uint16_t)(v & 0xffff); r.v[1] = (uint16_t)(v >> 16);
+  } else if constexpr (EPL == 4) {
+    const u32x2_t v = row_ld<NT>((const u32x2_t*)w);
+    r.v[0] = (uint16_t)(v.x & 0xffff); r.v[1] = (uint16_t)(v.x >> 16);
+    r.v[2] = (uint16_t)(v.y & 0xffff); r.v[3] = (uint16_t)(v.y >> 16);
+  } else if constexpr (EPL == 8) {
+    const u32x4_t v = row_ld<NT>((const u32x4_t*)w);
+    const uint32_t q[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      r.v[2 * i] = (uint16_t)(q[i] & 0xffff); r.v[2 * i + 1] = (uint16_t)(q[i] >> 16);
+    }
+  } else {
+    r.v[0] = row_ld<NT>(w);
+  }
+}
+
+// a lane's slice of table row `elem / D` as fp32, from an fp32 or a bf16 table
+template <int D, bool WB, bool NT = false>
+__device__ __forceinline__ void load_row_f(float (&wv)[BwdCfg<D>::EPL], const float* W,
+                                           uint64_t elem) {
+  if constexpr (WB) {
+    RowBits<D> r;
+    load_row_bits<D, NT>(r, (const uint16_t*)W + elem);
+#pragma unroll
+    for (int u = 0; u < BwdCfg<D>::EPL; ++u) wv[u] = bf2f(r.v[u]);
+  } else {
+    load_row<D, NT>(wv, W + elem);
+  }
+}
+
+// The row store of a bf16 table: nearest even, or stochastic rounding keyed
+// by (srk, row, column) -- never by lane, chunk or path.
+template <int D, bool NT>
+__device__ __forceinline__ void store_row_bits(const EmbBwdArgs& a, uint32_t srk, uint64_t row,
+                                               int e0, const float (&wv)[BwdCfg<D>::EPL]) {
+  constexpr int EPL = BwdCfg<D>::EPL;
+  uint16_t* w = (uint16_t*)a.W + row * D + e0;
+  uint32_t q[EPL];
+  const uint32_t rh = fold32(row);
+#pragma unroll
+  for (int u = 0; u < EPL; ++u)
+    q[u] = a.sr ? f2bf_sr(wv[u], srk, rh, (uint32_t)(e0 + u)) : f2bf(wv[u]);
+  if constexpr (EPL == 2) {
+    row_st<NT>((uint32_t*)w, q[0] | (q[1] << 16));
+  } else if constexpr (EPL == 4) {
+    row_st<NT>((u32x2_t*)w, u32x2_t{q[0] | (q[1] << 16), q[2] | (q[3] << 16)});
+  } else if constexpr (EPL == 8) {
+    row_st<NT>((u32x4_t*)w, u32x4_t{q[0] | (q[1] << 16), q[2] | (q[3] << 16),
+                                    q[4] | (q[5] << 16), q[6] | (q[7] << 16)});
+  } else {
+    row_st<NT>(w, (uint16_t)q[0]);
+  }
+}
+
 // raw gradient row slice (bf16 or fp32), branch-free
 template <int D, bool GB>
 struct GradRaw {
@@ -849,10 +967,15 @@ __device__ __forceinline__ float raw_f(const GradRaw<D, GB>& r, int u) {
   else return r.v[u];
 }
 
-struct OptScalars { float lr, bc1, bc2, gs; };
+struct OptScalars { float lr, bc1, bc2, gs; uint32_t srk; };
 
+// WB (bf16 table): also the key of this update's rounding stream, from the
+// counter the ids half advanced
+template <bool WB = false>
 __device__ __forceinline__ OptScalars opt_scalars(const EmbBwdArgs& a) {
   OptScalars o;
+  if constexpr (WB) o.srk = a.sr ? sr_key(a.sr_seed, (uint32_t)*a.sr_counter) : 0u;
+  else o.srk = 0u;
   o.lr = a.hyper[0];
   const float step = a.hyper[1];
   o.bc1 = 1.f - powf(a.beta1, step);
@@ -869,7 +992,7 @@ __device__ __forceinline__ bool skip_step(const EmbBwdArgs& a) {
 // One optimizer update of one row; `wv` = current weights (prefetched).
 // Adam with pre-loaded moments (mpre / vpre: this lane's elements of the
 // row's m and v, issued with the chunk's other loads) or loading them here.
-template <int D, int OPT, bool NT = false>
+template <int D, int OPT, bool NT = false, bool WB = false>
 __device__ __forceinline__ void update_row(const EmbBwdArgs& a, const OptScalars& o,
                                            uint64_t row, const float (&acc_in)[BwdCfg<D>::EPL],
                                            float (&wv)[BwdCfg<D>::EPL], float st_row, int lane,
@@ -930,7 +1053,9 @@ __device__ __forceinline__ void update_row(const EmbBwdArgs& a, const OptScalars
                          a.weight_decay * wv[u]);
       }
     }
-    if (act) {
+    if constexpr (WB) {
+      if (act) store_row_bits<D, NT>(a, o.srk, row, e0, wv);
+    } else if (act) {
       if constexpr (EPL == 2) {
         typedef __attribute__((ext_vector_type(2))) float f2v;
         row_st<NT>((f2v*)w, f2v{wv[0], wv[1]});
@@ -991,7 +1116,7 @@ __device__ __forceinline__ void part_load(float (&v)[EPL], const float* p) {
 // bits (inlined into two kernels with contraction on, the update came out
 // 1 ulp apart on 8 of 13 K rows; a non-inlined call cost the update kernel
 // 224 B of scratch and 20 us).
-template <int D, int OPT, int HQ_MAX = 32>
+template <int D, int OPT, int HQ_MAX = 32, bool WB = false>
 __device__ __forceinline__ void run_finish(const EmbBwdArgs& a, const OptScalars& o,
                                            int64_t cs, int64_t ce,
                            uint64_t row, float* head, float* tail, int lane) {
@@ -1021,9 +1146,9 @@ __device__ __forceinline__ void run_finish(const EmbBwdArgs& a, const OptScalars
   float wv[EPL];
 #pragma unroll
   for (int u = 0; u < EPL; ++u) wv[u] = 0.f;
-  if constexpr (OPT != EMB_DENSE_GRAD) load_row<D>(wv, a.W + row * D + e0c);
+  if constexpr (OPT != EMB_DENSE_GRAD) load_row_f<D, WB>(wv, a.W, row * D + e0c);
   const float st = OPT == EMB_ROWWISE_ADAGRAD ? a.state1[row] : 0.f;
-  update_row<D, OPT>(a, o, row, acc, wv, st, lane);
+  update_row<D, OPT, false, WB>(a, o, row, acc, wv, st, lane);
 }
 
 // One wave = one chunk of CH sorted entries. Every gradient row of the chunk
@@ -1034,7 +1159,8 @@ __device__ __forceinline__ void run_finish(const EmbBwdArgs& a, const OptScalars
 // head / tail partials: with run metadata (``meta``, from the one-hot sort)
 // the last of a run's chunks to arrive finishes it here; otherwise the
 // chunk where it starts is listed for emb_combine_kernel.
-template <int D, typename K, bool GB, int OPT, int CH, bool META = false, bool NT = false>
+template <int D, typename K, bool GB, int OPT, int CH, bool META = false, bool NT = false,
+          bool WB = false>
 __global__ __launch_bounds__(256) void emb_chunk_kernel(
     EmbBwdArgs a, const K* __restrict__ keys, const int32_t* __restrict__ vals,
     const int64_t* __restrict__ goff, const float* __restrict__ gscale,
@@ -1058,7 +1184,7 @@ __global__ __launch_bounds__(256) void emb_chunk_kernel(
     }
   }
   if (skip_step(a)) return;
-  const OptScalars o = opt_scalars(a);
+  const OptScalars o = opt_scalars<WB>(a);
   const int64_t nch = (a.nnz + CH - 1) / CH;
   const int64_t nwv = ((int64_t)nblk * blockDim.x) >> 6;
   // one wave per chunk (grid-stride: any grid size walks every chunk)
@@ -1090,7 +1216,8 @@ __global__ __launch_bounds__(256) void emb_chunk_kernel(
   const int e0c = act ? e0 : 0;
 
   GradRaw<D, GB> g[CH];
-  float wr[CH][EPL];
+  float wr[WB ? 1 : CH][EPL];
+  RowBits<D> wb[WB ? CH : 1];            // bf16 table: the rows as packed bits
   // Adam on narrow rows (one element per lane): the moments of every row of
   // the chunk are loaded up front too, not one dependent round trip per
   // finishing run (TwoTower / Bert4Rec, D = 16: a chunk's 32 updates waited
@@ -1102,7 +1229,8 @@ __global__ __launch_bounds__(256) void emb_chunk_kernel(
     const int64_t go = (int64_t)rdlane((uint64_t)mygoff, p);
     load_grad_raw<D, GB>(g[p], a.grad, go + e0c);
     const uint64_t rowp = (uint64_t)rdlane(mykey, p);
-    if constexpr (NEED_W) load_row<D, NT>(wr[p], a.W + rowp * D + e0c);
+    if constexpr (NEED_W && WB) load_row_bits<D, NT>(wb[p], (const uint16_t*)a.W + rowp * D + e0c);
+    else if constexpr (NEED_W) load_row<D, NT>(wr[p], a.W + rowp * D + e0c);
     if constexpr (PRE_MV) {
       mr[p][0] = a.state1[rowp * D + e0c];
       vr[p][0] = a.state2[rowp * D + e0c];
@@ -1121,13 +1249,16 @@ __global__ __launch_bounds__(256) void emb_chunk_kernel(
         if ((fmask >> p) & 1ull) {
           float wv[EPL];
 #pragma unroll
-          for (int u = 0; u < EPL; ++u) wv[u] = NEED_W ? wr[p][u] : 0.f;
+          for (int u = 0; u < EPL; ++u) {
+            if constexpr (WB) wv[u] = bf2f(wb[p].v[u]);
+            else wv[u] = NEED_W ? wr[p][u] : 0.f;
+          }
           if constexpr (PRE_MV)
             update_row<D, OPT, NT>(a, o, (uint64_t)rdlane(mykey, p), acc, wv, rdlanef(st_l, p),
                                    lane, mr[p], vr[p]);
           else
-            update_row<D, OPT, NT>(a, o, (uint64_t)rdlane(mykey, p), acc, wv, rdlanef(st_l, p),
-                                   lane);
+            update_row<D, OPT, NT, WB>(a, o, (uint64_t)rdlane(mykey, p), acc, wv,
+                                       rdlanef(st_l, p), lane);
         } else if (act) {
           part_store<EPL>(head + c * D + e0, acc);
         }
@@ -1168,9 +1299,9 @@ __global__ __launch_bounds__(256) void emb_chunk_kernel(
       if (lane == 0 && last_t) __hip_atomic_store(&rcnt[c], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     if (last_h)
-      run_finish<D, OPT>(a, o, hcs, hce, (uint64_t)rdlane(mykey, 0), head, tail, lane);
+      run_finish<D, OPT, 32, WB>(a, o, hcs, hce, (uint64_t)rdlane(mykey, 0), head, tail, lane);
     if (last_t)
-      run_finish<D, OPT>(a, o, c, tce, (uint64_t)rdlane(mykey, len - 1), head, tail, lane);
+      run_finish<D, OPT, 32, WB>(a, o, c, tce, (uint64_t)rdlane(mykey, len - 1), head, tail, lane);
   }
   }
 }
@@ -1188,7 +1319,7 @@ __global__ __launch_bounds__(256) void emb_chunk_kernel(
 constexpr int COMBINE_LONG = 256;
 constexpr int LONG_WAVES = 16;
 
-template <int D, typename K, int OPT, int CH>
+template <int D, typename K, int OPT, int CH, bool WB = false>
 __global__ __launch_bounds__(256) void emb_combine_kernel(
     EmbBwdArgs a, const K* __restrict__ keys, float* __restrict__ head,
     float* __restrict__ tail, const int32_t* __restrict__ tail_list,
@@ -1197,7 +1328,7 @@ __global__ __launch_bounds__(256) void emb_combine_kernel(
   const int nw = (gridDim.x * blockDim.x) >> 6;
   if (skip_step(a)) return;
   const int n = min(*tail_count, (int)((a.nnz + CH - 1) / CH));
-  const OptScalars o = opt_scalars(a);
+  const OptScalars o = opt_scalars<WB>(a);
   for (int i = ((blockIdx.x * blockDim.x + threadIdx.x) >> 6); i < n; i += nw) {
     const int64_t c = tail_list[i];
     const int64_t endc = min((c + 1) * CH, a.nnz);
@@ -1225,7 +1356,7 @@ __global__ __launch_bounds__(256) void emb_combine_kernel(
       }
       continue;
     }
-    run_finish<D, OPT>(a, o, c, jlast, (uint64_t)last, head, tail, lane);
+    run_finish<D, OPT, 32, WB>(a, o, c, jlast, (uint64_t)last, head, tail, lane);
   }
 }
 
@@ -1234,7 +1365,7 @@ __global__ __launch_bounds__(256) void emb_combine_kernel(
 // chunks in chunk order (HQ loads in flight), and wave 0 adds the run's tail
 // partial and the waves' sums in wave order, then applies the optimizer once.
 // Fixed order throughout: bitwise reproducible.
-template <int D, typename K, int OPT, int CH>
+template <int D, typename K, int OPT, int CH, bool WB = false>
 __global__ __launch_bounds__(64 * LONG_WAVES) void emb_combine_long_kernel(
     EmbBwdArgs a, const K* __restrict__ keys, const float* __restrict__ head,
     const float* __restrict__ tail, const int32_t* __restrict__ tail_count,
@@ -1247,7 +1378,7 @@ __global__ __launch_bounds__(64 * LONG_WAVES) void emb_combine_long_kernel(
   const int e0 = elem0<D>(lane);
   const bool act = D >= 64 || e0 < D;
   const int e0c = act ? e0 : 0;
-  const OptScalars o = opt_scalars(a);
+  const OptScalars o = opt_scalars<WB>(a);
   constexpr int HQ = EPL <= 2 ? 32 : (EPL <= 4 ? 16 : 8);
   for (int i = blockIdx.x; i < n; i += gridDim.x) {
     const int64_t c = long_list[2 * i], jlast = long_list[2 * i + 1];
@@ -1289,9 +1420,9 @@ __global__ __launch_bounds__(64 * LONG_WAVES) void emb_combine_long_kernel(
       float wv[EPL];
 #pragma unroll
       for (int u = 0; u < EPL; ++u) wv[u] = 0.f;
-      if constexpr (OPT != EMB_DENSE_GRAD) load_row<D>(wv, a.W + (uint64_t)last * D + e0c);
+      if constexpr (OPT != EMB_DENSE_GRAD) load_row_f<D, WB>(wv, a.W, (uint64_t)last * D + e0c);
       const float st = OPT == EMB_ROWWISE_ADAGRAD ? a.state1[(uint64_t)last] : 0.f;
-      update_row<D, OPT>(a, o, (uint64_t)last, t, wv, st, lane);
+      update_row<D, OPT, false, WB>(a, o, (uint64_t)last, t, wv, st, lane);
     }
     __syncthreads();                                   // part[] is reused
   }
@@ -1596,7 +1727,7 @@ PrepDone prep_impl(const EmbBwdArgs& a, const WsLayout& L, hipStream_t s) {
   return PrepDone{true};
 }
 
-template <int D, typename K, int OPT>
+template <int D, typename K, int OPT, bool WB = false>
 void apply_impl(const EmbBwdArgs& a0, const WsLayout& L, hipStream_t s) {
   EmbBwdArgs a = a0;
   a.goff_sorted = onehot_path(a0) && a0.segsort == 1;
@@ -1625,7 +1756,7 @@ void apply_impl(const EmbBwdArgs& a0, const WsLayout& L, hipStream_t s) {
       a.side_block0 = 0;
     }
 #define TDFO_CK(GBV, MV, NTV)                                                              \
-    hipLaunchKernelGGL((emb_chunk_kernel<D, K, GBV, OPT, CH, MV, NTV>), dim3(blocks), dim3(256), 0, \
+    hipLaunchKernelGGL((emb_chunk_kernel<D, K, GBV, OPT, CH, MV, NTV, WB>), dim3(blocks), dim3(256), 0, \
                        s, a, keys_out, vals_out, goff, gscale, head, tail, tlist, tcount, meta, rcnt)
     // non-temporal row accesses on multi-hot batches (see row_ld)
     const bool nt = g_emb_nt && !onehot_path(a0);
@@ -1646,14 +1777,14 @@ void apply_impl(const EmbBwdArgs& a0, const WsLayout& L, hipStream_t s) {
     // one id per bag (segsort = R sources): no run is longer than R x B ids
     const bool may_long =
         !(a.segsort > 0 && (int64_t)a.segsort * a.B <= (int64_t)COMBINE_LONG * CH);
-    hipLaunchKernelGGL((emb_combine_kernel<D, K, OPT, CH>), dim3(cblocks), dim3(256), 0, s, a,
+    hipLaunchKernelGGL((emb_combine_kernel<D, K, OPT, CH, WB>), dim3(cblocks), dim3(256), 0, s, a,
                        keys_out, head, tail, tlist, tcount, llist, (int)may_long);
     TDFO_CHECK_HIP(hipGetLastError());
     if (may_long) {
       // long runs: at most nch / COMBINE_LONG of them
       int64_t lblocks = nch / COMBINE_LONG + 1;
       if (lblocks > 256) lblocks = 256;
-      hipLaunchKernelGGL((emb_combine_long_kernel<D, K, OPT, CH>), dim3(lblocks),
+      hipLaunchKernelGGL((emb_combine_long_kernel<D, K, OPT, CH, WB>), dim3(lblocks),
                          dim3(64 * LONG_WAVES), 0, s, a, keys_out, head, tail, tcount, llist);
       TDFO_CHECK_HIP(hipGetLastError());
     }
@@ -1663,6 +1794,15 @@ void apply_impl(const EmbBwdArgs& a0, const WsLayout& L, hipStream_t s) {
 
 template <int D, typename K>
 void bwd_opt(const EmbBwdArgs& a, const WsLayout& L, hipStream_t s) {
+  if (a.w_bf16) {
+    // bf16 rows: SGD and row-wise Adagrad (fp32 row state), D = 64 / 128 / 256
+    if constexpr (D == 64 || D == 128 || D == 256) {
+      if (a.opt == EMB_SGD) return apply_impl<D, K, EMB_SGD, true>(a, L, s);
+      if (a.opt == EMB_ROWWISE_ADAGRAD) return apply_impl<D, K, EMB_ROWWISE_ADAGRAD, true>(a, L, s);
+    }
+    throw std::runtime_error("embedding_bwd: bf16 tables support SGD and row-wise Adagrad at "
+                             "D in {64, 128, 256}");
+  }
   switch (a.opt) {
     case EMB_SGD: apply_impl<D, K, EMB_SGD>(a, L, s); break;
     case EMB_ROWWISE_ADAGRAD: apply_impl<D, K, EMB_ROWWISE_ADAGRAD>(a, L, s); break;
@@ -1700,26 +1840,37 @@ void embedding_bag_fwd(const EmbFwdArgs& a, hipStream_t s) {
   const int64_t waves = (nbags * lpb + 63) / 64;
   int64_t blocks = (waves + 3) / 4;
   if (blocks > 8192) blocks = 8192;
-#define TDFO_EF(DD)                                                            \
+#define TDFO_EF2(DD, WBV)                                                      \
   if (a.onehot && !a.mean) {                                                   \
-    if (a.out_bf16) hipLaunchKernelGGL((emb_fwd_onehot_kernel<DD, true>),      \
+    if (a.out_bf16) hipLaunchKernelGGL((emb_fwd_onehot_kernel<DD, true, WBV>), \
                                        dim3(blocks), dim3(256), 0, s, a);      \
-    else hipLaunchKernelGGL((emb_fwd_onehot_kernel<DD, false>), dim3(blocks),  \
+    else hipLaunchKernelGGL((emb_fwd_onehot_kernel<DD, false, WBV>), dim3(blocks), \
                             dim3(256), 0, s, a);                               \
   } else if (rif == 8) {                                                       \
-    if (a.out_bf16) hipLaunchKernelGGL((emb_fwd_kernel<DD, true, 8>), dim3(blocks), \
+    if (a.out_bf16) hipLaunchKernelGGL((emb_fwd_kernel<DD, true, 8, WBV>), dim3(blocks), \
                                        dim3(256), 0, s, a);                    \
-    else hipLaunchKernelGGL((emb_fwd_kernel<DD, false, 8>), dim3(blocks),      \
+    else hipLaunchKernelGGL((emb_fwd_kernel<DD, false, 8, WBV>), dim3(blocks), \
                             dim3(256), 0, s, a);                               \
   } else if (rif == 16) {                                                      \
-    if (a.out_bf16) hipLaunchKernelGGL((emb_fwd_kernel<DD, true, 16>), dim3(blocks), \
+    if (a.out_bf16) hipLaunchKernelGGL((emb_fwd_kernel<DD, true, 16, WBV>), dim3(blocks), \
                                        dim3(256), 0, s, a);                    \
-    else hipLaunchKernelGGL((emb_fwd_kernel<DD, false, 16>), dim3(blocks),     \
+    else hipLaunchKernelGGL((emb_fwd_kernel<DD, false, 16, WBV>), dim3(blocks), \
                             dim3(256), 0, s, a);                               \
-  } else if (a.out_bf16) hipLaunchKernelGGL((emb_fwd_kernel<DD, true, 4>),     \
+  } else if (a.out_bf16) hipLaunchKernelGGL((emb_fwd_kernel<DD, true, 4, WBV>), \
                                             dim3(blocks), dim3(256), 0, s, a); \
-  else hipLaunchKernelGGL((emb_fwd_kernel<DD, false, 4>), dim3(blocks),        \
+  else hipLaunchKernelGGL((emb_fwd_kernel<DD, false, 4, WBV>), dim3(blocks),   \
                           dim3(256), 0, s, a)
+#define TDFO_EF(DD) TDFO_EF2(DD, false)
+  if (a.w_bf16) {                 // bf16 rows: D = 64 / 128 / 256
+    switch (a.D) {
+      case 64: TDFO_EF2(64, true); break;
+      case 128: TDFO_EF2(128, true); break;
+      case 256: TDFO_EF2(256, true); break;
+      default: throw std::runtime_error("embedding_bag_fwd: bf16 tables need D in {64, 128, 256}");
+    }
+    TDFO_CHECK_HIP(hipGetLastError());
+    return;
+  }
   switch (a.D) {
     case 16: TDFO_EF(16); break;
     case 32: TDFO_EF(32); break;
@@ -1729,6 +1880,7 @@ void embedding_bag_fwd(const EmbFwdArgs& a, hipStream_t s) {
     case 512: TDFO_EF(512); break;
   }
 #undef TDFO_EF
+#undef TDFO_EF2
   TDFO_CHECK_HIP(hipGetLastError());
 }
 

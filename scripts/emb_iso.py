@@ -7,6 +7,12 @@ D = 128, row-wise Adagrad) and DCN-v2 (same tables, MLPerf multi-hot pooling,
 reduce + optimizer), each graph-replayed alone, with the bytes each one must
 move and the achieved rate. Run under rocprofv3 --kernel-trace --stats for the
 per-kernel split. Uniform ids, as bench.py's synthetic batches.
+
+--table-dtype fp32|bf16|both: the row storage (bf16: 2-byte rows, stochastic
+rounding in the update). ``both`` holds the two tables side by side (135 GiB at
+the default shapes) and alternates them --repeats times per case in one
+process, one JSON line per (case, dtype, repeat), so the run-to-run spread
+stands next to the difference.
 """
 from __future__ import annotations
 
@@ -52,7 +58,12 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="dlrm,dcn")
     ap.add_argument("--batch", type=int, default=8192)
+    ap.add_argument("--table-dtype", choices=["fp32", "bf16", "both"], default="fp32")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timing rounds per case (default: 3 with both, else 1)")
     args = ap.parse_args()
+    dtypes = ["fp32", "bf16"] if args.table_dtype == "both" else [args.table_dtype]
+    repeats = args.repeats or (3 if len(dtypes) > 1 else 1)
     dev = "cuda"
     B, D = args.batch, 128
     rows = CRITEO_1TB_ROWS
@@ -61,8 +72,16 @@ def main():
     for r in rows[:-1]:
         ro_h.append(ro_h[-1] + r)
     total = ro_h[-1] + rows[-1]
-    W = torch.empty(total, D, device=dev)
-    W.uniform_(-0.01, 0.01)
+    W32 = torch.empty(total, D, device=dev)
+    W32.uniform_(-0.01, 0.01)
+    tabs = {}
+    if "bf16" in dtypes:
+        tabs["bf16"] = W32.to(torch.bfloat16)
+    if "fp32" in dtypes:
+        tabs["fp32"] = W32
+    del W32
+    esz = {"fp32": 4, "bf16": 2}
+    sr_step = torch.zeros((), dtype=torch.int64, device=dev)
     st = torch.zeros(total, device=dev)
     ro = torch.tensor(ro_h, dtype=torch.int64, device=dev)
     hyper = torch.tensor([1e-3, 1.0], device=dev)
@@ -84,14 +103,21 @@ def main():
         seg = 1 if onehot else 0
         bag_len = None if onehot else torch.tensor(L, dtype=torch.int32, device=dev)
         ws = torch.empty(ops.embedding_bwd_workspace(nnz, D), dtype=torch.uint8, device=dev)
-        fwd = lambda: ops.embedding_bag_fwd(W, ro, ids, offs, out_off, T, B, out, T * D,  # noqa
-                                            onehot=onehot)
-        prep = lambda: ops.embedding_bwd_prepare(W, ro, ids, offs, out_off, T, B, T * D, ws,  # noqa
-                                                 key_bits=kb, segsort=seg, bag_len=bag_len)
-        apply = lambda: ops.embedding_bwd_apply(W, ro, ids, offs, out_off, T, B, grad, T * D,  # noqa
-                                                ops.EMB_ROWWISE_ADAGRAD, hyper, ws, state1=st,
-                                                key_bits=kb, segsort=seg)
-        prep()
+
+        def calls(W):
+            srk = dict(sr_counter=sr_step) if W.dtype == torch.bfloat16 else {}
+            sra = dict(sr_seed=1234, stochastic_rounding=True, **srk) if srk else {}
+            fwd = lambda: ops.embedding_bag_fwd(W, ro, ids, offs, out_off, T, B, out, T * D,  # noqa
+                                                onehot=onehot)
+            prep = lambda: ops.embedding_bwd_prepare(W, ro, ids, offs, out_off, T, B, T * D,  # noqa
+                                                     ws, key_bits=kb, segsort=seg,
+                                                     bag_len=bag_len, **srk)
+            apply = lambda: ops.embedding_bwd_apply(W, ro, ids, offs, out_off, T, B, grad,  # noqa
+                                                    T * D, ops.EMB_ROWWISE_ADAGRAD, hyper, ws,
+                                                    state1=st, key_bits=kb, segsort=seg, **sra)
+            return fwd, prep, apply
+
+        calls(tabs[dtypes[0]])[1]()
         torch.cuda.synchronize()
         # bytes: fwd = rows read + pooled bf16 written; apply = grads read (bf16)
         # + unique rows read & written + row state read & written
@@ -99,21 +125,26 @@ def main():
         for t in range(T):
             s0, s1 = int(offs[t * B]), int(offs[(t + 1) * B])
             uniq += int(torch.unique(ids[s0:s1]).numel())
-        fwd_b = nnz * D * 4 + B * T * D * 2
-        app_b = nnz * D * 2 + uniq * (2 * D * 4 + 8)
-        tf = timeit(fwd)
-        tp = timeit(prep)
-        ta = timeit(apply)
+        for rep_i in range(repeats):
+            for dt in dtypes:                      # alternated inside every round
+                fwd, prep, apply = calls(tabs[dt])
+                fwd_b = nnz * D * esz[dt] + B * T * D * 2
+                app_b = nnz * D * 2 + uniq * (2 * D * esz[dt] + 8)
+                tf = timeit(fwd)
+                tp = timeit(prep)
+                ta = timeit(apply)
 
-        def both():
-            prep()
-            apply()
-        tb = timeit(both)
-        print(json.dumps({"case": case, "nnz": nnz, "unique_rows": uniq,
-                          "fwd_us": round(tf, 1), "fwd_TBps": round(fwd_b / tf / 1e6, 2),
-                          "prep_us": round(tp, 1), "apply_us": round(ta, 1),
-                          "apply_TBps": round(app_b / ta / 1e6, 2), "bwd_us": round(tb, 1)}),
-              flush=True)
+                def both():
+                    prep()
+                    apply()
+                tb = timeit(both)
+                print(json.dumps({"case": case, "table_dtype": dt, "repeat": rep_i, "nnz": nnz,
+                                  "unique_rows": uniq, "fwd_us": round(tf, 1),
+                                  "fwd_bytes": fwd_b, "fwd_TBps": round(fwd_b / tf / 1e6, 2),
+                                  "prep_us": round(tp, 1), "apply_us": round(ta, 1),
+                                  "apply_bytes": app_b,
+                                  "apply_TBps": round(app_b / ta / 1e6, 2),
+                                  "bwd_us": round(tb, 1)}), flush=True)
         del ws, out, grad, ids, offs
 
 

@@ -84,6 +84,7 @@ class Config:
     dcn_rank: int = 512
     emb_optimizer: str = "rowwise_adagrad"
     emb_learning_rate: float = 0.01
+    table_dtype: str = "fp32"         # dlrm / dcnv2 embedding row storage: fp32 | bf16
     dense_optimizer: str = "adamw"
     hip_graph: bool = True
     emb_update: str = "sparse"        # two_tower: sparse (fused row Adam) | dense (optax parity)
@@ -157,6 +158,10 @@ def validate(cfg: Config) -> None:
         raise ValueError("embed_dim and batch sizes must be positive")
     if cfg.model not in ("two_tower", "bert4rec", "dlrm", "dcnv2"):
         raise ValueError(f"unknown model {cfg.model!r}")
+    if cfg.table_dtype not in ("fp32", "bf16"):
+        raise ValueError(f"table_dtype must be fp32|bf16, got {cfg.table_dtype!r}")
+    if cfg.table_dtype == "bf16" and cfg.model not in ("dlrm", "dcnv2"):
+        raise ValueError("table_dtype = bf16 is supported by the dlrm and dcnv2 models only")
     if cfg.n_heads <= 0 or cfg.embed_dim % cfg.n_heads:          # torchrec/models.py:40
         raise ValueError("embed_dim must be divisible by n_heads")
 

@@ -85,6 +85,9 @@ class DLRMConfig:
     emb_opt: str = "rowwise_adagrad"
     emb_lr: float = 0.01
     emb_eps: float = 1e-8
+    table_dtype: str = "fp32"                      # embedding row storage: fp32 | bf16 (bf16:
+    #   half the row bytes, fp32 optimizer state, stochastically rounded updates; SGD /
+    #   row-wise Adagrad at D in {64, 128, 256}, table-wise / column-wise shards)
     sharding: str = "auto"                         # planner strategy
     rw_capacity: float = 1.25                      # initial row-wise segment capacity (x n/W);
     #   grown on demand before any exchange would overflow
@@ -290,11 +293,11 @@ class DLRMTrainer(StreamGraphsMixin, MultiRankStreamsMixin, DCNMixin):
         tables = cfg.tables()
         self.plan = plan or plan_sharding(tables, world_size, optim, batch_per_rank=B,
                                           pooling=cfg.pooling_factors(), strategy=cfg.sharding,
-                                          dp_rule=cfg.dp_rule)
+                                          dp_rule=cfg.dp_rule, table_dtype=cfg.table_dtype)
         self.emb = ShardedEmbeddingBags(tables, self.plan, rank, B, cfg.pooling_factors(), dev,
                                         optim, group=self.comm, seed=cfg.seed,
                                         rw_capacity=cfg.rw_capacity, rw_comm=cfg.rw_comm,
-                                        rw_exchange=cfg.rw_exchange)
+                                        rw_exchange=cfg.rw_exchange, table_dtype=cfg.table_dtype)
         if self.dcomm is not None:
             self.emb.dp_comm = self.dcomm         # replicated tables' all-reduce beside it
         # ------------------------------------------------------ dense params

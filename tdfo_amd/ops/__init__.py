@@ -376,22 +376,32 @@ def embedding_bag_fwd(W, row_offset, indices, offsets, out_off, T, B, out, out_s
 
 def embedding_bwd(W, row_offset, indices, offsets, grad_off, T, B, grad, grad_stride, opt, hyper,
                   state1=None, state2=None, eps=1e-8, beta1=0.9, beta2=0.999, weight_decay=0.0,
-                  key_bits=None, mean=False, psw=None, dense_grad=None, segsort=0):
+                  key_bits=None, mean=False, psw=None, dense_grad=None, segsort=0,
+                  sr_seed=0, sr_counter=None, stochastic_rounding=False):
     """Fused sort-based backward + optimizer. segsort=R > 0 promises one id
     per bag and that the T virtual tables are R runs (run-major) of T/R
     physical tables, only runs of the same table sharing rows; then per-table
-    LDS sorts (+ a run merge for R > 1) replace the device-wide radix sort."""
+    LDS sorts (+ a run merge for R > 1) replace the device-wide radix sort.
+
+    bf16 ``W`` (SGD / row-wise Adagrad, D in {64, 128, 256}): the update runs
+    in fp32 on the widened rows and the row store rounds -- to nearest even,
+    or with ``stochastic_rounding`` by 16 random bits that are a pure function
+    of (``sr_seed``, ``sr_counter``, global row, column). ``sr_counter`` (int64
+    scalar tensor on W's device, owned by the store) is advanced by one inside
+    the update, before it is used. fp32 tables ignore all three."""
     if key_bits is None:
         key_bits = key_bits_for(W.shape[0])
     if _gpu(W):
         segsort = effective_segsort(segsort)
         _native().embedding_bwd(W, row_offset, indices, offsets, grad_off, psw, T, B, mean,
                                 key_bits, grad, grad_stride, opt, state1, state2, hyper, eps,
-                                beta1, beta2, weight_decay, dense_grad, int(segsort))
+                                beta1, beta2, weight_decay, dense_grad, int(segsort),
+                                int(sr_seed), sr_counter, bool(stochastic_rounding))
     else:
         ref.embedding_bwd(W, row_offset, indices, offsets, grad_off, psw, T, B, mean, key_bits,
                           grad, grad_stride, opt, state1, state2, hyper, eps, beta1, beta2,
-                          weight_decay, dense_grad)
+                          weight_decay, dense_grad, sr_seed=int(sr_seed), sr_counter=sr_counter,
+                          stochastic_rounding=bool(stochastic_rounding))
 
 
 def embedding_bwd_workspace(nnz: int, D: int) -> int:
@@ -399,28 +409,36 @@ def embedding_bwd_workspace(nnz: int, D: int) -> int:
 
 
 def embedding_bwd_prepare(W, row_offset, indices, offsets, grad_off, T, B, grad_stride, workspace,
-                          key_bits=None, mean=False, psw=None, segsort=0, bag_len=None):
+                          key_bits=None, mean=False, psw=None, segsort=0, bag_len=None,
+                          sr_counter=None):
     """First half of the fused embedding backward (GPU): keys, sort and
     gradient offsets into ``workspace`` -- needs only the ids, so it can run
     on a side stream before the gradient exists. ``bag_len`` (int32 [T],
     optional): every bag of virtual table v holds bag_len[v] ids (fixed
-    multi-hot) -- the keys pass then divides instead of searching."""
+    multi-hot) -- the keys pass then divides instead of searching.
+    ``sr_counter`` (bf16 tables with stochastic rounding): advanced by one
+    here, in the half's first launch; the apply half reads it."""
     if key_bits is None:
         key_bits = key_bits_for(W.shape[0])
     _native().embedding_bwd_prepare(W, row_offset, indices, offsets, grad_off, psw, T, B, mean,
-                                    key_bits, grad_stride, int(segsort), workspace, bag_len)
+                                    key_bits, grad_stride, int(segsort), workspace, bag_len,
+                                    sr_counter)
 
 
 def embedding_bwd_apply(W, row_offset, indices, offsets, grad_off, T, B, grad, grad_stride, opt,
                         hyper, workspace, state1=None, state2=None, eps=1e-8, beta1=0.9,
                         beta2=0.999, weight_decay=0.0, key_bits=None, mean=False, psw=None,
-                        dense_grad=None, segsort=0):
-    """Second half: segment reduction + optimizer from a prepared workspace."""
+                        dense_grad=None, segsort=0, sr_seed=0, sr_counter=None,
+                        stochastic_rounding=False):
+    """Second half: segment reduction + optimizer from a prepared workspace.
+    bf16 tables: rounds with the counter value the prepare half left, so an
+    apply replayed without a new prepare reuses the same random bits."""
     if key_bits is None:
         key_bits = key_bits_for(W.shape[0])
     _native().embedding_bwd_apply(W, row_offset, indices, offsets, grad_off, psw, T, B, mean,
                                   key_bits, grad, grad_stride, opt, state1, state2, hyper, eps,
-                                  beta1, beta2, weight_decay, dense_grad, int(segsort), workspace)
+                                  beta1, beta2, weight_decay, dense_grad, int(segsort), workspace,
+                                  int(sr_seed), sr_counter, bool(stochastic_rounding))
 
 
 def embedding_dense_update(W, grad, rows, opt, hyper, state1=None, state2=None, eps=1e-8,
@@ -676,6 +694,21 @@ def auc_hist(logits, labels, nb, hist):
         _native().auc_hist(logits, labels, nb, hist)
     else:
         ref.auc_hist(logits, labels, nb, hist)
+
+
+def bf16_stochastic_round(x, seed, counter, row0=0, out=None):
+    """bf16 of the fp32 ``x`` [n, D] by the bf16 embedding tables' stochastic
+    rounding: element (i, c) takes r = hash3(seed ^ (counter * 0x632BE5AB),
+    fold32(row0 + i), c) & 0xFFFF and keeps (bits + r) >> 16; NaN and +-inf
+    round to nearest. ``counter``: int64 scalar tensor on x's device (read
+    only). One launch on the GPU, the integer mirror on the CPU."""
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
+    if _gpu(x):
+        _native().bf16_stochastic_round(x, int(seed), counter, int(row0), out)
+    else:
+        out.copy_(ref.bf16_stochastic_round(x, int(seed), int(counter), int(row0)))
+    return out
 
 
 def cast_bf16(x, y):

@@ -146,7 +146,12 @@ def embedding_grad_rows(W, row_offset, indices, offsets, grad_off, psw, T, B, me
 
 def embedding_bwd(W, row_offset, indices, offsets, grad_off, psw, T, B, mean, key_bits, grad,
                   grad_stride, opt, state1, state2, hyper, eps, beta1, beta2, weight_decay,
-                  dense_grad):
+                  dense_grad, sr_seed=0, sr_counter=None, stochastic_rounding=False):
+    wb = W.dtype == torch.bfloat16
+    if wb and opt not in (EMB_SGD, EMB_ROWWISE_ADAGRAD):
+        raise ValueError("bf16 embedding tables support EMB_SGD and EMB_ROWWISE_ADAGRAD only")
+    if wb and sr_counter is not None and indices.numel() > 0:
+        sr_counter.add_(1)          # (the kernels advance it in the ids half, skip or not)
     if hyper.numel() > 3 and float(hyper[3]) > 0:          # dynamic loss scale: skipped step
         return
     rows, g = embedding_grad_rows(W, row_offset, indices, offsets, grad_off, psw, T, B, mean,
@@ -156,7 +161,7 @@ def embedding_bwd(W, row_offset, indices, offsets, grad_off, psw, T, B, mean, ke
     if hyper.numel() > 2:
         g = g * float(hyper[2])                             # loss-scale unscale
     lr = float(hyper[0])
-    w = W[rows]
+    w = W[rows].float()             # bf16 rows: widened, the update runs in fp32
     if opt == EMB_SGD:
         w = w - lr * (g + weight_decay * w)
     elif opt == EMB_ROWWISE_ADAGRAD:
@@ -183,7 +188,42 @@ def embedding_bwd(W, row_offset, indices, offsets, grad_off, psw, T, B, mean, ke
         return
     else:
         raise ValueError(f"unknown embedding optimizer {opt}")
-    W[rows] = w
+    if wb and stochastic_rounding:
+        if sr_counter is None:
+            raise ValueError("stochastic rounding needs the store's sr_counter")
+        w = bf16_stochastic_round(w, sr_seed, int(sr_counter), rows=rows)
+    W[rows] = w.to(W.dtype)
+
+
+def _fold32(row):
+    """64-bit row index -> the hash's 32-bit row word (identity below 2^32)."""
+    return ((row & _M32) ^ (((row >> 32) & _M32) * 0x9E3779B1)) & _M32
+
+
+def bf16_sr_bits(seed: int, counter: int, rows, D: int):
+    """[len(rows), D] int64: the 16 random bits of every element of the given
+    global rows for update ``counter`` of a store seeded ``seed``."""
+    key = (int(seed) ^ ((int(counter) * 0x632BE5AB) & _M32)) & _M32
+    a = torch.full((1, 1), key, dtype=torch.int64, device=rows.device)
+    col = torch.arange(D, dtype=torch.int64, device=rows.device)[None, :]
+    return _hash3(a, _fold32(rows.to(torch.int64))[:, None], col) & 0xFFFF
+
+
+def bf16_stochastic_round(x, seed: int, counter: int, row0: int = 0, rows=None):
+    """Integer mirror of the kernels' stochastic f32 -> bf16 rounding
+    (csrc/include/tdfo_common.h, f2bf_sr): stored = (bits + r) >> 16 for finite
+    x, nearest-even for NaN / +-inf. ``rows``: the global row of every row of
+    x (default row0 + arange)."""
+    n, D = x.shape
+    if rows is None:
+        rows = torch.arange(n, dtype=torch.int64, device=x.device) + int(row0)
+    bits = x.contiguous().view(torch.int32).to(torch.int64) & _M32
+    r = bf16_sr_bits(seed, counter, rows, D)
+    hi = ((bits + r) >> 16) & 0xFFFF
+    hi = torch.where(hi >= 0x8000, hi - 0x10000, hi).to(torch.int16)
+    out = hi.view(torch.bfloat16)
+    nonfinite = (bits & 0x7F800000) == 0x7F800000
+    return torch.where(nonfinite, x.to(torch.bfloat16), out)
 
 
 def embedding_dense_update(W, grad, rows, opt, state1, state2, hyper, eps, beta1, beta2,

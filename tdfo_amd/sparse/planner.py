@@ -50,7 +50,7 @@ from __future__ import annotations
 from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional, Sequence
 
-from .tables import EmbOptimConfig, TableConfig
+from .tables import EmbOptimConfig, TableConfig, table_dtype_of
 
 HBM_BYTES = 288 * 10**9
 GiB = 1 << 30
@@ -90,8 +90,10 @@ class ShardingPlan:
                 "cost": [round(c, 3) for c in self.cost]}
 
 
-def _mem_per_row(dim: int, optim: EmbOptimConfig) -> int:
-    return 4 * (dim + optim.state_floats_per_row(dim))
+def _mem_per_row(dim: int, optim: EmbOptimConfig, elem_bytes: int = 4) -> int:
+    """Bytes of one row: ``elem_bytes`` per element (4 fp32, 2 bf16) plus the
+    optimizer state, which is fp32 for either."""
+    return elem_bytes * dim + 4 * optim.state_floats_per_row(dim)
 
 
 def plan_sharding(tables: Sequence[TableConfig], world_size: int, optim: EmbOptimConfig,
@@ -101,8 +103,13 @@ def plan_sharding(tables: Sequence[TableConfig], world_size: int, optim: EmbOpti
                   row_cost: Optional[Callable[[int], float]] = None,
                   dp_max_rows: Optional[int] = None,
                   dp_replicate_max_bytes: int = 256 << 20,
-                  balance: float = 1.10, dp_rule: str = "cost") -> ShardingPlan:
+                  balance: float = 1.10, dp_rule: str = "cost",
+                  table_dtype: str = "fp32") -> ShardingPlan:
     """Deterministic greedy planner with a balance pass.
+
+    table_dtype: "fp32" | "bf16" -- the element size behind every memory
+    figure (optimizer state stays fp32). Placement kinds are not restricted
+    here; the engine refuses a bf16 table placed row-wise or data-parallel.
 
     strategy: "auto" (table-wise with row-wise fallback for tables that fit
     no rank), "table_wise", "row_wise", "column_wise" (tables split evenly by
@@ -139,7 +146,8 @@ def plan_sharding(tables: Sequence[TableConfig], world_size: int, optim: EmbOpti
     kw = dict(batch_per_rank=batch_per_rank, pooling=pooling, hbm_bytes=hbm_bytes,
               reserve_frac=reserve_frac, strategy=strategy, dp_max_bytes=dp_max_bytes,
               row_cost=row_cost, dp_max_rows=dp_max_rows,
-              dp_replicate_max_bytes=dp_replicate_max_bytes, dp_rule=dp_rule)
+              dp_replicate_max_bytes=dp_replicate_max_bytes, dp_rule=dp_rule,
+              elem_bytes=table_dtype_of(table_dtype)[1])
     plan = _plan_once(tables, world_size, optim, frozenset(), **kw)
     if strategy != "auto" or world_size == 1 or balance is None:
         return plan
@@ -168,7 +176,7 @@ def plan_sharding(tables: Sequence[TableConfig], world_size: int, optim: EmbOpti
 
 def _plan_once(tables, world_size, optim, force_rw, batch_per_rank, pooling, hbm_bytes,
                reserve_frac, strategy, dp_max_bytes, row_cost, dp_max_rows,
-               dp_replicate_max_bytes, dp_rule="cost") -> ShardingPlan:
+               dp_replicate_max_bytes, dp_rule="cost", elem_bytes=4) -> ShardingPlan:
     W = world_size
     cap = int(hbm_bytes * (1.0 - reserve_frac))
     T = len(tables)
@@ -206,7 +214,7 @@ def _plan_once(tables, world_size, optim, force_rw, batch_per_rank, pooling, hbm
         # checkpoint manifests); every rank allocates the largest share
         blk = -(-rows // W)
         blocks = [len(range(r, rows, W)) for r in range(W)]
-        per_row = _mem_per_row(tables[t].embedding_dim, optim)
+        per_row = _mem_per_row(tables[t].embedding_dim, optim, elem_bytes)
         for r in range(W):
             mem[r] += (blk + 1) * per_row   # padded block + scratch row (every rank)
             cost[r] += rcost(t)
@@ -220,7 +228,7 @@ def _plan_once(tables, world_size, optim, force_rw, batch_per_rank, pooling, hbm
         cols = [d // nb] * nb
         ranks = sorted(range(W), key=lambda r: (cost[r], mem[r], r))[:nb]
         for i, r in enumerate(ranks):
-            mem[r] += tables[t].num_embeddings * 4 * (cols[i] + optim.state_floats_per_row(cols[i]))
+            mem[r] += tables[t].num_embeddings * _mem_per_row(cols[i], optim, elem_bytes)
             cost[r] += tcost(t) * cols[i] / d
         return TableShard(t, "column_wise", ranks, col_blocks=cols)
 
@@ -229,7 +237,7 @@ def _plan_once(tables, world_size, optim, force_rw, batch_per_rank, pooling, hbm
     if strategy == "auto" and W > 1:
         for t in order:
             if t in force_rw or (tables[t].num_embeddings *
-                                 _mem_per_row(tables[t].embedding_dim, optim) > cap):
+                                 _mem_per_row(tables[t].embedding_dim, optim, elem_bytes) > cap):
                 shards[t] = row_wise(t)
     # "data_parallel": the smallest tables are replicated while their fp32
     # weights add up to at most dp_replicate_max_bytes -- the replicated set
@@ -256,7 +264,7 @@ def _plan_once(tables, world_size, optim, force_rw, batch_per_rank, pooling, hbm
         cum = 0
         for t in sorted(range(T), key=lambda t: (tables[t].num_embeddings *
                                                   tables[t].embedding_dim, t)):
-            nb = tables[t].num_embeddings * tables[t].embedding_dim * 4
+            nb = tables[t].bytes_at(elem_bytes)
             if cum + nb > dp_replicate_max_bytes or (dp_rule == "cost" and not ar_cheaper(t)):
                 break
             cum += nb
@@ -264,7 +272,7 @@ def _plan_once(tables, world_size, optim, force_rw, batch_per_rank, pooling, hbm
     for t in order:
         if shards[t] is not None:
             continue
-        tb = tables[t].num_embeddings * _mem_per_row(tables[t].embedding_dim, optim)
+        tb = tables[t].num_embeddings * _mem_per_row(tables[t].embedding_dim, optim, elem_bytes)
         if strategy == "data_parallel" and W > 1 and t not in replicate:
             shards[t] = row_wise(t)                 # owner-partitioned big table
             continue

@@ -45,7 +45,7 @@ import torch
 from .. import ops
 from ..parallel.comm import as_comm
 from .planner import ShardingPlan
-from .tables import EmbOptimConfig, TableBatchedEmbedding, TableConfig
+from .tables import EmbOptimConfig, TableBatchedEmbedding, TableConfig, table_dtype_of
 
 
 _WARNED_SKIP_RW_READ = False
@@ -64,8 +64,13 @@ class ShardedEmbeddingBags:
                  batch_size: int, pooling: Sequence[int], device, optim: EmbOptimConfig,
                  group=None, seed: int = 0, mean: bool = False, rw_capacity: float = 1.25,
                  rw_comm: str = "bf16", dp_dense_max_bytes: int = 256 << 20,
-                 recv_dtype: str = "bf16", rw_exchange: str = "auto"):
-        """``rw_capacity``: initial per-owner segment capacity of the row-wise
+                 recv_dtype: str = "bf16", rw_exchange: str = "auto",
+                 table_dtype: str = "fp32"):
+        """``table_dtype``: "fp32" | "bf16" storage of the table rows (see
+        ``TableBatchedEmbedding``). bf16 covers table-wise and column-wise
+        shards at any world size; a plan that places a table row-wise or
+        data-parallel at world size > 1 raises NotImplementedError.
+        ``rw_capacity``: initial per-owner segment capacity of the row-wise
         exchange as a multiple of the uniform share n/W (+256). Before every
         exchange the largest per-owner count is all-reduced and the capacity
         grows (buffers reallocated, ``layout_version`` bumped, the batch
@@ -105,6 +110,18 @@ class ShardedEmbeddingBags:
         for s in plan.shards:
             if s.kind not in ("table_wise", "row_wise", "data_parallel", "column_wise"):
                 raise NotImplementedError(f"sharding kind {s.kind} not supported for pooled bags")
+        self.table_dtype = table_dtype
+        wdt = table_dtype_of(table_dtype)[0]
+        if wdt == torch.bfloat16:
+            bad = [(self.tables[s.table].name, s.kind) for s in plan.shards
+                   if s.kind == "row_wise" or (s.kind == "data_parallel" and plan.world_size > 1)]
+            if bad:
+                raise NotImplementedError(
+                    "bf16 embedding tables are supported table-wise and column-wise (any world "
+                    "size) and on a single rank; the plan places " +
+                    ", ".join(f"{n} {k}" for n, k in bad) +
+                    ": keep these tables fp32, or plan with strategy='table_wise' / "
+                    "'column_wise' and dp_max_rows=0")
         # ---- id layout in the input (original order)
         self.in_base = [0] * self.T
         acc = 0
@@ -141,7 +158,7 @@ class ShardedEmbeddingBags:
                                               init_ranges=[self.tables[t].init_range or
                                                            (1.0 / self.tables[t].num_embeddings) ** 0.5
                                                            for t in mine],
-                                              seed=seed * 1000 + rank)
+                                              seed=seed * 1000 + rank, dtype=wdt)
         # send order: tables grouped by owner
         order = [t for r in range(W) for t in self.tw_tables[r]]
         self.tw_send_counts = [sum(B * self.L[t] for t in self.tw_tables[r]) for r in range(W)]
@@ -201,7 +218,7 @@ class ShardedEmbeddingBags:
             self.cw_store = TableBatchedEmbedding(
                 [self.tables[t].num_embeddings for t, _ in cmine], Dc, device, optim,
                 init_ranges=[self.tables[t].init_range or (1.0 / self.tables[t].num_embeddings) ** 0.5
-                             for t, _ in cmine], seed=seed * 1000 + 300 + rank)
+                             for t, _ in cmine], seed=seed * 1000 + 300 + rank, dtype=wdt)
             corder = [t for r in range(W) for t, _ in self.cw_owned[r]]
             self.cw_send_counts = [sum(B * self.L[t] for t, _ in self.cw_owned[r]) for r in range(W)]
             self.cw_recv_count = sum(B * self.L[t] for t, _ in cmine)
@@ -302,7 +319,8 @@ class ShardedEmbeddingBags:
             self.dp_store = TableBatchedEmbedding(
                 [self.tables[t].num_embeddings for t in dpt], D, device, optim,
                 init_ranges=[self.tables[t].init_range or (1.0 / self.tables[t].num_embeddings) ** 0.5
-                             for t in dpt], seed=seed * 1000 + 777)        # same on all ranks
+                             for t in dpt], seed=seed * 1000 + 777,        # same on all ranks
+                dtype=wdt)
             self.dp_in_idx = torch.cat([torch.arange(self.in_base[t], self.in_base[t] + B * self.L[t])
                                         for t in dpt]).to(self.device)
             self.dp_in_map = ops.SegmentMap(self._runs(dpt), self.device)

@@ -61,7 +61,8 @@ def dlrm_config(cfg: Config, strategy: str) -> DLRMConfig:
                       dcn_layers=cfg.dcn_layers, dcn_rank=cfg.dcn_rank,
                       dense_opt=cfg.dense_optimizer, dense_lr=cfg.learning_rate,
                       dense_wd=cfg.weight_decay, emb_opt=cfg.emb_optimizer,
-                      emb_lr=cfg.emb_learning_rate, sharding=strategy, seed=cfg.seed)
+                      emb_lr=cfg.emb_learning_rate, table_dtype=cfg.table_dtype,
+                      sharding=strategy, seed=cfg.seed)
 
 
 def _source(cfg: Config, dcfg: DLRMConfig, B: int, device, rank: int, stream: int,

@@ -48,15 +48,36 @@ def _piece_name(t: int, lo: int, hi: int, step: int, c0: int, c1: int) -> str:
 
 
 def _write_rows(path: Path, view: torch.Tensor, chunk_bytes: int):
-    """Stream ``view`` ([rows] or [rows, cols], any device) to a raw fp32 file."""
+    """Stream ``view`` ([rows] or [rows, cols], any device) to a raw file of
+    its element type: fp32, or the 16-bit patterns of a bf16 table."""
     rows = view.shape[0]
-    per_row = max(1, (view.numel() // max(1, rows)) * 4)
+    bf16 = view.dtype == torch.bfloat16
+    per_row = max(1, (view.numel() // max(1, rows)) * (2 if bf16 else 4))
     step = max(1, chunk_bytes // per_row)
     tmp = path.with_suffix(path.suffix + ".tmp")
     with open(tmp, "wb") as f:
         for r0 in range(0, rows, step):
-            view[r0: r0 + step].detach().to("cpu", torch.float32).contiguous().numpy().tofile(f)
+            blk = view[r0: r0 + step].detach()
+            if bf16:
+                blk.contiguous().view(torch.int16).cpu().numpy().tofile(f)
+            else:
+                blk.to("cpu", torch.float32).contiguous().numpy().tofile(f)
     os.replace(tmp, path)
+
+
+def _from_file(arr: np.ndarray, bf16: bool) -> torch.Tensor:
+    """Rows read from a piece file as a tensor (bf16 files hold bit patterns)."""
+    t = torch.from_numpy(np.array(arr))
+    return t.view(torch.bfloat16) if bf16 else t
+
+
+def _sr_step(emb) -> int:
+    """Update counter of the rounding stream of bf16 stores (they advance in
+    lockstep, once per step; a store without ids never reads it)."""
+    steps = [int(st.sr_step) for st in (getattr(emb, n, None) for n in
+                                        ("tw_store", "cw_store", "dp_store"))
+             if st is not None and getattr(st, "sr_step", None) is not None]
+    return max(steps, default=0)
 
 
 def local_pieces(emb) -> List[Dict]:
@@ -107,7 +128,8 @@ def save(tr, dirpath: str, step: int, rank: int, world: int, meta: Optional[Dict
             files[name] = base + (".s1.bin" if name == "state1" else ".s2.bin")
             _write_rows(d / files[name], view, chunk_bytes)
         index.append({k: p[k] for k in ("table", "lo", "hi", "step", "c0", "c1")} |
-                     {"files": files, "state1_rowwise": bool("state1" in p["states"] and
+                     {"files": files, "weight_dtype": "bf16" if p["weight"].dtype ==
+                      torch.bfloat16 else "fp32", "state1_rowwise": bool("state1" in p["states"] and
                                                              p["states"]["state1"].dim() == 1)})
     (d / f"rank_{rank:05d}.json").write_text(json.dumps(index))
     if rank == 0:
@@ -123,6 +145,7 @@ def save(tr, dirpath: str, step: int, rank: int, world: int, meta: Optional[Dict
                "tables": [{"name": t.name, "rows": t.num_embeddings, "dim": t.embedding_dim}
                           for t in emb.tables],
                "optimizer": emb.optim.name,
+               "table_dtype": getattr(emb, "table_dtype", "fp32"), "sr_step": _sr_step(emb),
                "plan": [{"table": s.table, "kind": s.kind, "ranks": list(s.ranks),
                          "row_blocks": list(s.row_blocks), "col_blocks": list(s.col_blocks)}
                         for s in emb.plan.shards],
@@ -151,24 +174,25 @@ def _rows(sp: Dict) -> range:
 
 
 def _copy_region(dst: torch.Tensor, d: Path, sp: Dict, fname: str, lo: int, hi: int, c0: int,
-                 c1: int, rowwise: bool, chunk_bytes: int, accumulate_weight: float = 0.0):
+                 c1: int, rowwise: bool, chunk_bytes: int, accumulate_weight: float = 0.0,
+                 bf16: bool = False):
     """dst[rows lo..hi of the table, cols c0..c1] <- saved contiguous piece
     ``sp`` (the caller passes the intersection). ``rowwise``: dst is a [rows]
     state; with accumulate_weight > 0 it is accumulated (width-weighted mean)."""
     rows_s = sp["hi"] - sp["lo"]
     cols_s = sp["c1"] - sp["c0"]
     shape = (rows_s,) if rowwise else (rows_s, cols_s)
-    mm = np.memmap(d / fname, dtype=np.float32, mode="r", shape=shape)
-    per_row = max(1, (c1 - c0) * 4)
+    mm = np.memmap(d / fname, dtype=np.int16 if bf16 else np.float32, mode="r", shape=shape)
+    per_row = max(1, (c1 - c0) * (2 if bf16 else 4))
     step = max(1, chunk_bytes // per_row)
     for r0 in range(lo, hi, step):
         r1 = min(hi, r0 + step)
         if rowwise:
-            src = torch.from_numpy(np.array(mm[r0 - sp["lo"]: r1 - sp["lo"]]))
+            src = _from_file(mm[r0 - sp["lo"]: r1 - sp["lo"]], bf16)
         else:
-            src = torch.from_numpy(np.array(mm[r0 - sp["lo"]: r1 - sp["lo"],
-                                               c0 - sp["c0"]: c1 - sp["c0"]]))
-        src = src.to(dst.device)
+            src = _from_file(mm[r0 - sp["lo"]: r1 - sp["lo"], c0 - sp["c0"]: c1 - sp["c0"]], bf16)
+        src = src.to(dst.device)               # (the assignment converts: an fp32 piece into
+        #                                         a bf16 table rounds to nearest, bf16 widens)
         if rowwise and accumulate_weight:
             dst[r0 - lo: r1 - lo] += accumulate_weight * src
         else:
@@ -186,7 +210,8 @@ def _copy_strided(p: Dict, d: Path, sp: Dict, chunk_bytes: int) -> int:
     if cl >= ch or not pr or not srows:
         return 0
     n_s, w_s = len(srows), sp["c1"] - sp["c0"]
-    per_row = max(1, (p["c1"] - p["c0"]) * 4)
+    wbf = sp.get("weight_dtype", "fp32") == "bf16"
+    per_row = max(1, (p["c1"] - p["c0"]) * (2 if wbf else 4))
     chunk = max(1, chunk_bytes // per_row)
     covered = 0
     files = {"weight": (p["weight"], False)}
@@ -194,7 +219,8 @@ def _copy_strided(p: Dict, d: Path, sp: Dict, chunk_bytes: int) -> int:
         if name not in sp["files"]:
             raise ValueError(f"checkpoint piece of table {p['table']} lacks {name}")
         files[name] = (view, view.dim() == 1)
-    mms = {k: np.memmap(d / sp["files"][k], dtype=np.float32, mode="r",
+    mms = {k: np.memmap(d / sp["files"][k],
+                        dtype=np.int16 if (wbf and k == "weight") else np.float32, mode="r",
                         shape=(n_s,) if rw else (n_s, w_s)) for k, (_, rw) in files.items()}
     sst = sp.get("step", 1)
     for k0 in range(0, len(pr), chunk):
@@ -213,7 +239,8 @@ def _copy_strided(p: Dict, d: Path, sp: Dict, chunk_bytes: int) -> int:
                 view[li] += ((ch - cl) / (p["c1"] - p["c0"])) * vals
             else:
                 vals = np.asarray(mms[k][src][:, cl - sp["c0"]: ch - sp["c0"]])
-                view[li, cl - p["c0"]: ch - p["c0"]] = torch.from_numpy(vals).to(view.device)
+                view[li, cl - p["c0"]: ch - p["c0"]] = _from_file(
+                    vals, wbf and k == "weight").to(view.device).to(view.dtype)
     del mms
     return covered
 
@@ -257,7 +284,8 @@ def load(tr, dirpath: str, rank: int, world: int, expect_meta: Optional[Dict] = 
                     continue
                 covered += (rh - rl) * (ch - cl)
                 _copy_region(p["weight"][rl - lo: rh - lo, cl - c0: ch - c0], d, sp,
-                             sp["files"]["weight"], rl, rh, cl, ch, False, chunk_bytes)
+                             sp["files"]["weight"], rl, rh, cl, ch, False, chunk_bytes,
+                             bf16=sp.get("weight_dtype", "fp32") == "bf16")
                 for name, view in p["states"].items():
                     if name not in sp["files"]:
                         raise ValueError(f"checkpoint piece of table {t} lacks {name}")
@@ -272,6 +300,10 @@ def load(tr, dirpath: str, rank: int, world: int, expect_meta: Optional[Dict] = 
             if covered != want:
                 raise ValueError(f"checkpoint does not cover table {t} rows {_rows(p)} "
                                  f"cols [{c0},{c1}) ({covered} of {want})")
+        for name in ("tw_store", "cw_store", "dp_store"):      # bf16 stores: rounding stream
+            st = getattr(emb, name, None)
+            if st is not None and getattr(st, "sr_step", None) is not None:
+                st.sr_step.fill_(int(man.get("sr_step", 0)))
         dense = torch.load(d / "dense.pt", map_location="cpu", weights_only=True)
         tr.load_dense_state(dense)
     return int(man["step"])
