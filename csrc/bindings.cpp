@@ -1697,8 +1697,10 @@ void linear_xent(const Tensor& H, const Tensor& W, const Tensor& bias, const Ten
                  const std::vector<double>& oparams, int64_t okind) {
   check_dev(H, "H");
   TORCH_CHECK(H.scalar_type() == at::kFloat && H.dim() == 2 &&
-              (H.size(1) == 16 || H.size(1) == 32 || H.size(1) == 64) &&
-              H.is_contiguous() && aligned16(H.data_ptr()), "linear_xent: H fp32 [N,16|32|64]");
+              (H.size(1) == 16 || H.size(1) == 32 || H.size(1) == 64 || H.size(1) == 128 ||
+               H.size(1) == 256) &&
+              H.is_contiguous() && aligned16(H.data_ptr()),
+              "linear_xent: H fp32 [N,16|32|64|128|256]");
   const int64_t N = H.size(0), V = W.size(0), E = H.size(1);
   TORCH_CHECK(W.scalar_type() == at::kFloat && W.dim() == 2 && W.size(1) == E &&
               W.is_contiguous() && aligned16(W.data_ptr()), "linear_xent: W fp32 [V,E]");
@@ -1755,6 +1757,13 @@ void linear_xent(const Tensor& H, const Tensor& W, const Tensor& bias, const Ten
     a.ohyper = ohyper->data_ptr<float>();
     a.beta1 = (float)oparams[0]; a.beta2 = (float)oparams[1];
     a.oeps = (float)oparams[2]; a.owd = (float)oparams[3];
+  }
+  if (E >= 128) {                  // hidden 128 / 256: linear_xent_mfma.hip
+    Tensor ws = at::empty({(int64_t)tdfo::linear_xent_mfma_workspace((int)N, V, (int)E)},
+                          H.options().dtype(at::kByte));
+    a.workspace = ws.data_ptr();
+    tdfo::linear_xent_mfma(a, (int)E, cur_stream());
+    return;
   }
   if (E != 16) {                   // hidden 32 / 64: linear_xent_wide.hip
     Tensor ws = at::empty({(int64_t)tdfo::linear_xent_wide_workspace((int)N, V, (int)E)},
@@ -1919,6 +1928,8 @@ TORCH_LIBRARY(tdfo, m) {
         "Tensor(b!) out_scores, int v_lo, int v_hi, Tensor? exclude, Tensor? target, "
         "Tensor(c!)? out_rank) -> ()");
   m.def("topk_splits(int n) -> int", [](int64_t n) { return (int64_t)tdfo::topk_splits((int)n); });
+  m.def("linear_xent_splits(int n) -> int",
+        [](int64_t n) { return (int64_t)tdfo::linear_xent_splits((int)n); });
   m.def("layernorm_parts(int M) -> int", [](int64_t M) { return (int64_t)tdfo::layernorm_parts(M); });
   m.def("gather_columns(Tensor[] src, Tensor? idx, int row0, int n, Tensor(a!)[] dst, int[] dst_stride) -> ()");
   m.def("concat_features(Tensor dense, Tensor emb, int[] off, int[] stride, int F, int D, "

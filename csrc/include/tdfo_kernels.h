@@ -486,6 +486,13 @@ size_t linear_xent_workspace(int N, int64_t V);
 // VALU kernels (the MFMA kernels of linear_xent.hip are built around E = 16).
 size_t linear_xent_wide_workspace(int N, int64_t V, int E);
 void linear_xent_wide(const LinearXentArgs& a, int E, hipStream_t s);
+// Hidden widths 128 and 256 (linear_xent_mfma.hip): the same contract on
+// exact-f32 MFMA kernels tiled over E. linear_xent_splits: vocab splits of its
+// pass1, 0 auto, n > 0 forces n ranges of V (clamped to V); n < 0 only reads
+// it. Returns the previous value. The workspace size depends on it.
+size_t linear_xent_mfma_workspace(int N, int64_t V, int E);
+void linear_xent_mfma(const LinearXentArgs& a, int E, hipStream_t s);
+int linear_xent_splits(int n);
 // 1: f32-input MFMA pass1/wgrad (default), 0: VALU kernels; <0 queries.
 // Returns the previous setting.
 int linear_xent_impl(int impl);

@@ -48,8 +48,24 @@ METRICS_K = (10, 20, 50)
 # and every LayerNorm run as hand-written kernels (csrc/kernels/attention.hip,
 # attention_long.hip above T = 64, layernorm.hip); on CPU the same modules run
 # the torch reference ops. Supported on the GPU: max_len <= 512, embed_dim in
-# {16, 32, 64}, embed_dim / heads in {4, 8, 16, 32, 64}, max_len * embed_dim <= 32768.
+# {16, 32, 64, 128, 256}, embed_dim / heads in {4, 8, 16, 32, 64},
+# max_len * embed_dim <= 32768 (check_gpu_shape).
 USE_FUSED = True
+GPU_EMBED_DIMS = (16, 32, 64, 128, 256)   # ops.linear_xent's kernels (output layer + loss)
+GPU_MAX_ROW = 32768                       # joint [T, E] LayerNorm / input block row
+
+
+def check_gpu_shape(max_len: int, embed_dim: int, n_heads: int) -> None:
+    """Raise ValueError unless the GPU kernels cover this Bert4Rec shape (the
+    CPU path has no such limits)."""
+    ok = (embed_dim in GPU_EMBED_DIMS and n_heads > 0 and embed_dim % n_heads == 0
+          and embed_dim // n_heads in ops.ATTN_DK and 0 < max_len <= ops.ATTN_LONG_MAXT
+          and max_len * embed_dim <= GPU_MAX_ROW)
+    if not ok:
+        raise ValueError(
+            f"Bert4Rec on the GPU supports embed_dim in {GPU_EMBED_DIMS}, d_k = embed_dim / "
+            f"heads in {ops.ATTN_DK}, max_len <= {ops.ATTN_LONG_MAXT} and max_len * embed_dim <= "
+            f"{GPU_MAX_ROW}; got embed_dim = {embed_dim}, heads = {n_heads}, max_len = {max_len}")
 # whole transformer block in one fwd / one bwd kernel (encoder.hip); False
 # keeps the per-op path (fused attention core + LayerNorm kernels, torch GEMMs)
 USE_FUSED_BLOCK = True
@@ -512,6 +528,8 @@ class Bert4RecTrainer:
         self.V = n_items + 2                     # 0 = PAD, n_items + 1 = MASK
         self.T, self.E, self.B = max_len, embed_dim, batch_size
         self.device = dev = torch.device(device)
+        if dev.type == "cuda":
+            check_gpu_shape(max_len, embed_dim, n_heads)
         self.mode, self.group, self.rank, self.world = mode, group, rank, world
         self.eps = label_smoothing
         torch.manual_seed(seed)
@@ -747,16 +765,14 @@ class Bert4RecTrainer:
         if self.mode == "dmp" and B < self.B:     # sharded engine has a static shape
             pad = torch.zeros(self.B - B, self.T, dtype=seqs.dtype, device=seqs.device)
             seqs = torch.cat([seqs, pad])
-        h = self.model.encode(self._embed(seqs), seqs)[:B, -1, :].contiguous()
-        if h.is_cuda and self.E not in (16, 32, 64):
-            raise ValueError("full-catalogue search on the GPU needs embed_dim in (16, 32, 64)")
-        return h
+        return self.model.encode(self._embed(seqs), seqs)[:B, -1, :].contiguous()
 
     @torch.no_grad()
     def recommend(self, seqs: torch.Tensor, k: int, exclude_seen: bool = True):
         """The k best items for every sequence [B, T] over the whole catalogue
         (ids 1 .. n_items: PAD and MASK are not eligible), scored from the
-        last-position hidden state by the fused search (no [B, V] logits).
+        last-position hidden state by the fused search (no [B, V] logits; at
+        embed_dim 128 / 256 by ops.topk_scores' chunked torch fallback).
         exclude_seen drops the items of the sequence itself. Returns
         (ids int64 [B, k], scores fp32 [B, k]), best first, ties by lower id;
         rows with fewer than k eligible items end in -1 / -inf."""

@@ -875,7 +875,8 @@ def reduce_adam(part, nparts, n, ld, grad, p, m, v, hyper, beta1=0.9, beta2=0.99
 def linear_xent(H, W, bias, labels, eps, ignore, dH, lossv, dW=None, db=None, loss=None,
                 loss_acc=None, step=None):
     """Fused Linear(E->V) + label-smoothed CrossEntropy, fwd+bwd (no logits);
-    on the GPU E = 16 (MFMA kernels) or 32 / 64 (linear_xent_wide.hip).
+    on the GPU E = 16 (MFMA kernels), 32 / 64 (linear_xent_wide.hip) or
+    128 / 256 (linear_xent_mfma.hip).
     loss (fp32 [1]): mean loss over the non-ignored tokens; loss_acc (fp64
     [1]): += that loss (device running sum). step = (opt, [mW, vW, mb, vb],
     hyper, beta1, beta2, eps, weight_decay): apply the flat optimizer's
@@ -902,6 +903,15 @@ def linear_xent(H, W, bias, labels, eps, ignore, dH, lossv, dW=None, db=None, lo
             for p, g, m, v in ((W, dW, st[0], st[1]), (bias, db, st[2], st[3])):
                 ref.dense_optimizer(p.view(-1), g.view(-1), m.view(-1), v.view(-1), None, opt,
                                     hyper, b1, b2, oeps, wd, 0.0, None)
+
+
+def linear_xent_splits(n: int = -1) -> int:
+    """Vocab splits of the hidden 128 / 256 Linear+CE kernels
+    (csrc/kernels/linear_xent_mfma.hip): 0 auto (default), n > 0 forces n
+    (clamped to V); n < 0 only reads it. Returns the previous value. Results
+    differ between split counts only by fp32 association; for a fixed count
+    they are bit-reproducible. Other widths do not look at it."""
+    return int(_native().linear_xent_splits(int(n)))
 
 
 def jagged_to_dense(values, offsets, T, pad, out):
@@ -996,6 +1006,9 @@ def rank_metrics(h, W, bias, cand, ks, out):
         ref.rank_metrics(h, W, bias, cand, ks, out)
 
 
+TOPK_FALLBACK_E = (128, 256)   # no fused search at these widths: chunked torch on the device
+
+
 def topk_splits(n: int = -1) -> int:
     """Ranges of V the top-K search is split over (csrc/kernels/retrieval.hip):
     0 auto (default), n > 0 forces n (clamped to 64 and to the number of
@@ -1017,9 +1030,16 @@ def topk_scores(q, W, bias, k, out_ids, out_scores, v_lo=0, v_hi=None, exclude=N
     eligible items other than target[b] whose score is >= the target's (the
     pessimistic tie rule of ``rank_metrics``). The target is scored like any
     item even if it is in exclude[b] or outside [v_lo, v_hi): it is ranked as
-    if it were eligible. Scores must be finite."""
+    if it were eligible. Scores must be finite.
+
+    The fused search (csrc/kernels/retrieval.hip) covers E in (16, 32, 64). At
+    E = 128 / 256 device tensors take the chunked reference on the device (a
+    fallback in torch: the same total order and padding, one [B, chunk] score
+    block at a time)."""
     v_hi = W.shape[0] if v_hi is None else v_hi
-    if _gpu(q):
+    if _gpu(q) and q.shape[-1] in TOPK_FALLBACK_E:
+        ref.topk_scores(q, W, bias, k, out_ids, out_scores, v_lo, v_hi, exclude, target, out_rank)
+    elif _gpu(q):
         _native().topk_scores(q, W, bias, int(k), out_ids, out_scores, int(v_lo), int(v_hi),
                               exclude, target, out_rank)
     else:
