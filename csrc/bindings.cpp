@@ -511,7 +511,7 @@ void topk_scores(const Tensor& q, const Tensor& W, const c10::optional<Tensor>& 
   TORCH_CHECK(q.dim() == 2 && W.dim() == 2 && q.size(1) == W.size(1),
               "topk_scores: q [B, E], W [V, E]");
   const int64_t B = q.size(0), E = q.size(1), V = W.size(0);
-  TORCH_CHECK(E == 16 || E == 32 || E == 64, "topk_scores: E must be 16, 32 or 64");
+  TORCH_CHECK(E <= 256 && tdfo::topk_width_ok((int)E), TDFO_TOPK_WIDTHS_MSG);
   TORCH_CHECK(V >= 1 && V <= INT32_MAX && B <= INT32_MAX, "topk_scores: 1 <= V < 2^31");
   TORCH_CHECK(k >= 1 && k <= 128, "topk_scores: 1 <= k <= 128");
   TORCH_CHECK(0 <= v_lo && v_lo <= v_hi && v_hi <= V, "topk_scores: 0 <= v_lo <= v_hi <= V");
@@ -552,7 +552,7 @@ void topk_scores(const Tensor& q, const Tensor& W, const c10::optional<Tensor>& 
     rp = out_rank->data_ptr<int64_t>();
   }
   if (B == 0) return;
-  const tdfo::TopkPlan plan = tdfo::topk_plan((int)B, (int)v_lo, (int)v_hi);
+  const tdfo::TopkPlan plan = tdfo::topk_plan((int)B, (int)E, (int)v_lo, (int)v_hi);
   Tensor part = at::empty({B * plan.S * k}, out_ids.options());
   Tensor cpart, tscore, excl_ge;
   if (tp != nullptr) {

@@ -628,20 +628,24 @@ void jagged_ids_to_dense(const int64_t* values, const int64_t* off, int B, int T
 
 // ------------------------------------------------- retrieval (top-K) ----
 // Full-catalogue search (retrieval.hip): for every query row b of Q [B, E]
-// (E in {16, 32, 64}), scores Q[b] . W[v] (+ bias[v]) over v in [v_lo, v_hi)
+// (E in {16, 32, 64, 128, 256}), scores Q[b] . W[v] (+ bias[v]) over v in [v_lo, v_hi)
 // minus the ids in exclude[b, 0..X) (entries < 0 are padding); ids / scores
 // [B, K] = the K <= 128 best under (score descending, id ascending), padded
 // with -1 / -inf; with target [B], rank[b] = number of eligible items other
 // than target[b] scoring >= it (target[b] itself may be excluded or outside
 // [v_lo, v_hi): it is scored all the same; outside [0, V): rank 0).
-// Scratch (the caller allocates; plan = topk_plan(B, v_lo, v_hi)):
+// Scratch (the caller allocates; plan = topk_plan(B, E, v_lo, v_hi): a block
+// holds 64 queries at E <= 64 and 32 at E = 128 / 256, and auto S is about
+// one block per CU):
 // part [B * S * K] 64-bit, cpart [S * B] int32, tscore [B] fp32, excl_ge [B]
 // int32 (the last three only with a target).
 // topk_splits: 0 auto, n > 0 forces S = n ranges of V (clamped to 64 and to
 // the number of 128-item tiles), n < 0 only reads; returns the previous value.
+#define TDFO_TOPK_WIDTHS_MSG "topk_scores: E must be one of 16, 32, 64, 128, 256"
 struct TopkPlan { int S; int span; };
 int topk_splits(int n);
-TopkPlan topk_plan(int B, int v_lo, int v_hi);
+bool topk_width_ok(int E);
+TopkPlan topk_plan(int B, int E, int v_lo, int v_hi);
 void topk_scores(const float* Q, const float* W, const float* bias, const int64_t* exclude,
                  const int64_t* target, int B, int V, int E, int X, int K, int v_lo, int v_hi,
                  const TopkPlan& plan, uint64_t* part, int* cpart, float* tscore, int* excl_ge,

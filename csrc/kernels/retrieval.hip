@@ -15,7 +15,10 @@
 // topk_scan_kernel: one block = 64 queries (4 A tiles kept in registers) x one
 // of S ranges of V; 8 waves, each streams 16 item rows per iteration straight
 // from global / L2 and reuses the B fragment for the 4 A tiles (4 independent
-// accumulators). A (score, id) pair is one 64-bit key whose integer order is
+// accumulators). At E = 128 / 256 a block holds 32 queries (2 A tiles: E / 2
+// registers per lane, half the candidate LDS) and an item row passes through
+// a ring of two 64-element groups instead of waiting whole in registers; the
+// chain's order over e is the same (c, j, g). A (score, id) pair is one 64-bit key whose integer order is
 // the total order. Per query row LDS holds a threshold key (the current K-th
 // best) and 256 candidate slots. A score is first compared with the
 // threshold's score (one float compare); only where a lane of the wave passes
@@ -40,8 +43,10 @@ namespace tdfo {
 namespace {
 
 constexpr int TK_WAVES = 8;
-constexpr int TK_NT = 4;
-constexpr int TK_QT = 16 * TK_NT;       // queries per block
+// query tiles (of 16) a block keeps in registers: E / 4 * NT registers per lane
+constexpr int tk_nt(int E) { return E <= 64 ? 4 : 2; }
+constexpr int tk_qt(int E) { return 16 * tk_nt(E); }   // queries per block
+constexpr int TK_GC = 4;                // wide E: 16-element chunks of an item row per load group
 constexpr int TK_IT = 16 * TK_WAVES;    // items per block iteration
 constexpr int TK_CAP = 256;             // candidate slots per query
 constexpr int TK_MAXS = 64;
@@ -262,6 +267,8 @@ __device__ __forceinline__ void tk_final(const TopkArgs& a, uint64_t* buf, int* 
 
 template <int E, bool HAS_T>
 __global__ __launch_bounds__(64 * TK_WAVES) void topk_scan_kernel(TopkArgs a) {
+  constexpr int TK_NT = tk_nt(E), TK_QT = tk_qt(E);
+  constexpr bool WIDE = E > 64;
   extern __shared__ __attribute__((aligned(16))) char tk_smem[];
   uint64_t* buf = (uint64_t*)tk_smem;          // [TK_QT][TK_CAP]
   uint64_t* thr = buf + TK_QT * TK_CAP;        // [TK_QT]
@@ -304,15 +311,29 @@ __global__ __launch_bounds__(64 * TK_WAVES) void topk_scan_kernel(TopkArgs a) {
   // item rows PF block iterations ahead, in registers (6 ahead measured no
   // faster than 1: profiles/retrieval.md; kept small for registers)
   constexpr int PF = E == 16 ? 2 : 1;
-  TkFrag<E> wq[PF];
+  TkFrag<WIDE ? 16 : E> wq[PF];
   float bq[PF];
+  // wide E: an item row does not wait whole in registers. It comes in groups
+  // of TK_GC chunks through a ring of two; the last group of a row is
+  // multiplied while the first group of the wave's next row loads into wg[0]
+  // (the number of groups is even), wrow = the row the ring is reading.
+  constexpr int NG = E / 16 / TK_GC;
+  static_assert(!WIDE || (NG >= 2 && NG % 2 == 0 && PF == 1), "ring of two groups");
+  float4 wg[2][TK_GC];
+  const float* wrow = a.W;
 #pragma unroll
   for (int u = 0; u < PF; ++u) {
     bq[u] = 0.f;
     const int v = vbeg + u * TK_IT + 16 * w + col;
     if (vbeg + u * TK_IT < vend) {
       const int vr = v < vend ? v : vend - 1;
-      wq[u] = tk_load<E>(a.W + (int64_t)vr * E, g);
+      if constexpr (WIDE) {
+        wrow = a.W + (int64_t)vr * E + 4 * g;
+#pragma unroll
+        for (int cc = 0; cc < TK_GC; ++cc) wg[0][cc] = *(const float4*)(wrow + 16 * cc);
+      } else {
+        wq[u] = tk_load<E>(a.W + (int64_t)vr * E, g);
+      }
       bq[u] = v < vend ? (a.bias ? a.bias[vr] : 0.f) : __builtin_nanf("");
     }
   }
@@ -323,27 +344,61 @@ __global__ __launch_bounds__(64 * TK_WAVES) void topk_scan_kernel(TopkArgs a) {
     const int vb = vb0 + u * TK_IT;
     if (vb >= vend) break;
     const int v = vb + 16 * w + col;
-    const TkFrag<E> wb = wq[u];
     const float bv = bq[u];
-    if (vb + PF * TK_IT < vend) {
-      const int v2 = v + PF * TK_IT;
-      const int vr = v2 < vend ? v2 : vend - 1;
-      wq[u] = tk_load<E>(a.W + (int64_t)vr * E, g);
-      bq[u] = v2 < vend ? (a.bias ? a.bias[vr] : 0.f) : __builtin_nanf("");
-    }
     f32x4_t acc[TK_NT];
 #pragma unroll
     for (int tt = 0; tt < TK_NT; ++tt) acc[tt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    if constexpr (WIDE) {
+      const bool more = vb + TK_IT < vend;
+      const int v2 = v + TK_IT;
+      const int vr2 = v2 < vend ? v2 : vend - 1;     // (read only if more)
 #pragma unroll
-    for (int c = 0; c < E / 16; ++c) {
+      for (int gi = 0; gi < NG; ++gi) {
+        if (gi + 1 < NG) {
 #pragma unroll
-      for (int tt = 0; tt < TK_NT; ++tt) acc[tt] = tk_mfma(qa[tt].v[c].x, wb.v[c].x, acc[tt]);
+          for (int cc = 0; cc < TK_GC; ++cc)
+            wg[(gi + 1) & 1][cc] = *(const float4*)(wrow + 16 * (TK_GC * (gi + 1) + cc));
+        } else if (more) {
+          wrow = a.W + (int64_t)vr2 * E + 4 * g;
 #pragma unroll
-      for (int tt = 0; tt < TK_NT; ++tt) acc[tt] = tk_mfma(qa[tt].v[c].y, wb.v[c].y, acc[tt]);
+          for (int cc = 0; cc < TK_GC; ++cc) wg[0][cc] = *(const float4*)(wrow + 16 * cc);
+          bq[0] = v2 < vend ? (a.bias ? a.bias[vr2] : 0.f) : __builtin_nanf("");
+        }
+        // the loads stay a whole group (16 MFMA steps per tile) ahead of their use
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int tt = 0; tt < TK_NT; ++tt) acc[tt] = tk_mfma(qa[tt].v[c].z, wb.v[c].z, acc[tt]);
+        for (int cc = 0; cc < TK_GC; ++cc) {
+          const int c = TK_GC * gi + cc;
+          const float4 wv = wg[gi & 1][cc];
 #pragma unroll
-      for (int tt = 0; tt < TK_NT; ++tt) acc[tt] = tk_mfma(qa[tt].v[c].w, wb.v[c].w, acc[tt]);
+          for (int tt = 0; tt < TK_NT; ++tt) acc[tt] = tk_mfma(qa[tt].v[c].x, wv.x, acc[tt]);
+#pragma unroll
+          for (int tt = 0; tt < TK_NT; ++tt) acc[tt] = tk_mfma(qa[tt].v[c].y, wv.y, acc[tt]);
+#pragma unroll
+          for (int tt = 0; tt < TK_NT; ++tt) acc[tt] = tk_mfma(qa[tt].v[c].z, wv.z, acc[tt]);
+#pragma unroll
+          for (int tt = 0; tt < TK_NT; ++tt) acc[tt] = tk_mfma(qa[tt].v[c].w, wv.w, acc[tt]);
+        }
+      }
+    } else {
+      const TkFrag<E> wb = wq[u];
+      if (vb + PF * TK_IT < vend) {
+        const int v2 = v + PF * TK_IT;
+        const int vr = v2 < vend ? v2 : vend - 1;
+        wq[u] = tk_load<E>(a.W + (int64_t)vr * E, g);
+        bq[u] = v2 < vend ? (a.bias ? a.bias[vr] : 0.f) : __builtin_nanf("");
+      }
+#pragma unroll
+      for (int c = 0; c < E / 16; ++c) {
+#pragma unroll
+        for (int tt = 0; tt < TK_NT; ++tt) acc[tt] = tk_mfma(qa[tt].v[c].x, wb.v[c].x, acc[tt]);
+#pragma unroll
+        for (int tt = 0; tt < TK_NT; ++tt) acc[tt] = tk_mfma(qa[tt].v[c].y, wb.v[c].y, acc[tt]);
+#pragma unroll
+        for (int tt = 0; tt < TK_NT; ++tt) acc[tt] = tk_mfma(qa[tt].v[c].z, wb.v[c].z, acc[tt]);
+#pragma unroll
+        for (int tt = 0; tt < TK_NT; ++tt) acc[tt] = tk_mfma(qa[tt].v[c].w, wb.v[c].w, acc[tt]);
+      }
     }
     __syncthreads();                            // the previous iteration's compactions are done
     // A score first meets its row's threshold score (one compare; an item
@@ -480,9 +535,12 @@ int topk_splits(int n) {
   return old;
 }
 
-TopkPlan topk_plan(int B, int v_lo, int v_hi) {
+bool topk_width_ok(int E) { return E == 16 || E == 32 || E == 64 || E == 128 || E == 256; }
+
+TopkPlan topk_plan(int B, int E, int v_lo, int v_hi) {
   const int64_t tiles = ((int64_t)v_hi - v_lo + TK_IT - 1) / TK_IT;
-  const int nqt = (B + TK_QT - 1) / TK_QT;
+  const int qt = tk_qt(E);
+  const int nqt = (B + qt - 1) / qt;
   int64_t S = g_topk_splits > 0 ? g_topk_splits : (256 + nqt - 1) / (nqt < 1 ? 1 : nqt);
   if (S > TK_MAXS) S = TK_MAXS;
   if (S > tiles) S = tiles;
@@ -507,8 +565,9 @@ void topk_scores(const float* Q, const float* W, const float* bias, const int64_
     throw std::runtime_error("topk_scores: bad split plan");
   TopkArgs a{Q, W, bias, X > 0 ? exclude : nullptr, target, B, V, X > 0 ? X : 0, K, v_lo, v_hi,
              plan.S, plan.span, part, cpart, tscore, excl_ge};
-  const int nqt = (B + TK_QT - 1) / TK_QT;
-  const size_t sm = (size_t)TK_QT * TK_CAP * 8 + TK_QT * (8 + 4 + 4 + 4) + 16;
+  if (!topk_width_ok(E)) throw std::runtime_error(TDFO_TOPK_WIDTHS_MSG);
+  const int qt = tk_qt(E), nqt = (B + qt - 1) / qt;
+  const size_t sm = (size_t)qt * TK_CAP * 8 + qt * (8 + 4 + 4 + 4) + 16;
   const size_t msm = (size_t)plan.S * K * (8 + 4) + 16;
   const bool has_t = target != nullptr;
 #define TDFO_TK(EE)                                                                          \
@@ -534,7 +593,9 @@ void topk_scores(const float* Q, const float* W, const float* bias, const int64_
     case 16: TDFO_TK(16); break;
     case 32: TDFO_TK(32); break;
     case 64: TDFO_TK(64); break;
-    default: throw std::runtime_error("topk_scores: E must be 16, 32 or 64");
+    case 128: TDFO_TK(128); break;
+    case 256: TDFO_TK(256); break;
+    default: throw std::runtime_error(TDFO_TOPK_WIDTHS_MSG);
   }
 #undef TDFO_TK
   TDFO_CHECK_HIP(hipGetLastError());

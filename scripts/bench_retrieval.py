@@ -1,12 +1,17 @@
 """Microbenchmark of the fused full-catalogue top-K search (ops.topk_scores)
 against stock eager ``torch.topk(q @ W.T + b, k)`` on the same GPU (chunked
 over B where the [B, V] score matrix would not fit), at the Bert4Rec and
-TwoTower catalogue shapes. One JSON line per shape:
-fused / eager time, the fused time's share of the f32-MFMA time
-2 B V E / 155 TF and of one HBM pass over W at 6.3 TB/s, and (with --splits)
-the time under forced numbers of V ranges."""
+TwoTower catalogue shapes, at the embedding width --embed-dim. One JSON line
+per shape: fused / eager time, the fused time's share of the f32-MFMA time
+2 B V E / 155 TF and of one HBM pass over W at 6.3 TB/s, (with --splits) the
+time under forced numbers of V ranges and (with --fallback) the time of the
+chunked torch reference on the same device tensors, which is what
+ops.topk_scores ran at E = 128 / 256 before the fused search covered them.
+--rounds n times fused, fallback and eager n times each, alternating, and
+reports the median with the range."""
 import argparse
 import json
+import statistics
 import sys
 import time
 from pathlib import Path
@@ -18,7 +23,7 @@ from tdfo_amd import ops  # noqa: E402
 
 PEAK_F32_MFMA = 155e12      # FLOP/s
 PEAK_HBM = 6.3e12           # B/s
-SHAPES = {"bert4rec": (1_000_002, 16, 256, 100), "two_tower": (2_360_650, 16, 2048, 100)}
+SHAPES = {"bert4rec": (1_000_002, 256, 100), "two_tower": (2_360_650, 2048, 100)}   # V, B, K
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--shape", default="", help="bert4rec | two_tower (default: both)")
@@ -27,6 +32,11 @@ ap.add_argument("--iters", type=int, default=20)
 ap.add_argument("--eager-score-bytes", type=float, default=4e9,
                 help="largest eager score matrix: B is chunked to stay below it")
 ap.add_argument("--no-torch", action="store_true")
+ap.add_argument("--embed-dim", type=int, default=16, choices=ops.topk_fused_widths())
+ap.add_argument("--fallback", action="store_true",
+                help="also time ops.reference.topk_scores on the device tensors")
+ap.add_argument("--rounds", type=int, default=1,
+                help="alternating timing rounds per variant (median and range reported)")
 args = ap.parse_args()
 assert torch.cuda.is_available(), "bench_retrieval needs a GPU"
 dev = "cuda"
@@ -43,7 +53,15 @@ def timed(fn, iters):
     return (time.perf_counter() - t) / iters * 1e6
 
 
-for name, (V, E, B, K) in SHAPES.items():
+def summary(rec, key, xs):
+    """Median under `key`; with several rounds the range too."""
+    rec[key] = round(statistics.median(xs), 1)
+    if len(xs) > 1:
+        rec[key + "_range"] = [round(min(xs), 1), round(max(xs), 1)]
+
+
+E = args.embed_dim
+for name, (V, B, K) in SHAPES.items():
     if args.shape and name != args.shape:
         continue
     g = torch.Generator(device=dev).manual_seed(0)
@@ -56,9 +74,29 @@ for name, (V, E, B, K) in SHAPES.items():
     def fused():
         ops.topk_scores(q, W, b, K, ids, sc)
 
+    fids = torch.empty(B, K, dtype=torch.int64, device=dev)
+    fsc = torch.empty(B, K, device=dev)
+
+    def fallback():
+        ops.reference.topk_scores(q, W, b, K, fids, fsc)
+
+    cb = max(1, min(B, int(args.eager_score_bytes // (4 * V))))
+
+    def eager():
+        out = [torch.topk(q[i: i + cb] @ W.t() + b, K) for i in range(0, B, cb)]
+        return out
+
     rec = {"shape": name, "V": V, "E": E, "B": B, "K": K}
-    us = timed(fused, args.iters)
-    rec["fused_us"] = round(us, 1)
+    few = max(2, args.iters // 4)
+    t_fused, t_fb, t_eager = [], [], []
+    for _ in range(max(1, args.rounds)):
+        t_fused.append(timed(fused, args.iters))
+        if args.fallback:
+            t_fb.append(timed(fallback, few))
+        if not args.no_torch:
+            t_eager.append(timed(eager, few))
+    summary(rec, "fused_us", t_fused)
+    us = statistics.median(t_fused)
     t_mfma = 2.0 * B * V * E / PEAK_F32_MFMA * 1e6
     t_hbm = V * E * 4 / PEAK_HBM * 1e6
     rec["f32_mfma_floor_us"] = round(t_mfma, 1)
@@ -69,15 +107,17 @@ for name, (V, E, B, K) in SHAPES.items():
         old = ops.topk_splits(s)
         rec[f"fused_us_splits_{s}"] = round(timed(fused, args.iters), 1)
         ops.topk_splits(old)
+    if args.fallback:
+        summary(rec, "fallback_us", t_fb)
+        rec["speedup_vs_fallback"] = round(rec["fallback_us"] / us, 2)
+        fused()
+        fallback()
+        torch.cuda.synchronize()
+        rec["fallback_same_ids"] = bool(torch.equal(fids, ids))
+        rec["fallback_max_abs_score_diff"] = float((fsc - sc).abs().max())
     if not args.no_torch:
-        cb = max(1, min(B, int(args.eager_score_bytes // (4 * V))))
-
-        def eager():
-            out = [torch.topk(q[i: i + cb] @ W.t() + b, K) for i in range(0, B, cb)]
-            return out
-
         rec["eager_chunk_B"] = cb
-        rec["eager_us"] = round(timed(eager, max(2, args.iters // 4)), 1)
+        summary(rec, "eager_us", t_eager)
         rec["speedup"] = round(rec["eager_us"] / us, 2)
         # same answer (ties aside: random floats)
         fused()

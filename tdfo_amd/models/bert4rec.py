@@ -771,8 +771,8 @@ class Bert4RecTrainer:
     def recommend(self, seqs: torch.Tensor, k: int, exclude_seen: bool = True):
         """The k best items for every sequence [B, T] over the whole catalogue
         (ids 1 .. n_items: PAD and MASK are not eligible), scored from the
-        last-position hidden state by the fused search (no [B, V] logits; at
-        embed_dim 128 / 256 by ops.topk_scores' chunked torch fallback).
+        last-position hidden state by the fused search (no [B, V] logits, at
+        every embed_dim the trainer accepts).
         exclude_seen drops the items of the sequence itself. Returns
         (ids int64 [B, k], scores fp32 [B, k]), best first, ties by lower id;
         rows with fewer than k eligible items end in -1 / -inf."""

@@ -1006,13 +1006,20 @@ def rank_metrics(h, W, bias, cand, ks, out):
         ref.rank_metrics(h, W, bias, cand, ks, out)
 
 
-TOPK_FALLBACK_E = (128, 256)   # no fused search at these widths: chunked torch on the device
+TOPK_FUSED_E = (16, 32, 64, 128, 256)   # widths csrc/kernels/retrieval.hip is instantiated at
+
+
+def topk_fused_widths():
+    """Embedding widths E the fused top-K search (``topk_scores`` on device
+    tensors) supports; any other width on the device is an error."""
+    return TOPK_FUSED_E
 
 
 def topk_splits(n: int = -1) -> int:
     """Ranges of V the top-K search is split over (csrc/kernels/retrieval.hip):
-    0 auto (default), n > 0 forces n (clamped to 64 and to the number of
-    128-item tiles); n < 0 only reads it. Returns the previous value. Results
+    0 auto (default: about one block per CU at the width's query tile), n > 0
+    forces n at every width (clamped to 64 and to the number of 128-item
+    tiles); n < 0 only reads it. Returns the previous value. Results
     do not depend on it."""
     return int(_native().topk_splits(int(n)))
 
@@ -1032,14 +1039,13 @@ def topk_scores(q, W, bias, k, out_ids, out_scores, v_lo=0, v_hi=None, exclude=N
     item even if it is in exclude[b] or outside [v_lo, v_hi): it is ranked as
     if it were eligible. Scores must be finite.
 
-    The fused search (csrc/kernels/retrieval.hip) covers E in (16, 32, 64). At
-    E = 128 / 256 device tensors take the chunked reference on the device (a
-    fallback in torch: the same total order and padding, one [B, chunk] score
-    block at a time)."""
+    Device tensors take the fused search (csrc/kernels/retrieval.hip) at every
+    E in ``topk_fused_widths()`` = (16, 32, 64, 128, 256); a block holds 64
+    queries at E <= 64 and 32 at E = 128 / 256. Any other width on the device
+    raises. CPU tensors take the chunked reference (one [B, chunk] score block
+    at a time, any E)."""
     v_hi = W.shape[0] if v_hi is None else v_hi
-    if _gpu(q) and q.shape[-1] in TOPK_FALLBACK_E:
-        ref.topk_scores(q, W, bias, k, out_ids, out_scores, v_lo, v_hi, exclude, target, out_rank)
-    elif _gpu(q):
+    if _gpu(q):
         _native().topk_scores(q, W, bias, int(k), out_ids, out_scores, int(v_lo), int(v_hi),
                               exclude, target, out_rank)
     else:
