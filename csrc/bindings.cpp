@@ -259,8 +259,9 @@ void attn_lse(tdfo::AttnArgs& a, const c10::optional<Tensor>& lse) {
 
 void attention_fwd(const Tensor& qkv, const Tensor& ids, int64_t H, double rate, int64_t seed,
                    const c10::optional<Tensor>& step, int64_t pad_id, const Tensor& out,
-                   const c10::optional<Tensor>& lse) {
+                   const c10::optional<Tensor>& lse, bool causal) {
   auto a = attn_args(qkv, ids, H, rate, seed, step, pad_id);
+  a.causal = causal ? 1 : 0;
   check_dev(out, "out");
   TORCH_CHECK(out.scalar_type() == at::kFloat && out.is_contiguous() &&
               out.numel() == qkv.numel() / 3, "attention: out fp32 [B, T, E]");
@@ -272,8 +273,9 @@ void attention_fwd(const Tensor& qkv, const Tensor& ids, int64_t H, double rate,
 void attention_bwd(const Tensor& qkv, const Tensor& ids, const Tensor& dout, int64_t H,
                    double rate, int64_t seed, const c10::optional<Tensor>& step, int64_t pad_id,
                    const Tensor& dqkv, const c10::optional<Tensor>& out,
-                   const c10::optional<Tensor>& lse) {
+                   const c10::optional<Tensor>& lse, bool causal) {
   auto a = attn_args(qkv, ids, H, rate, seed, step, pad_id);
+  a.causal = causal ? 1 : 0;
   if (a.T > tdfo::ATTN_SHORT_MAXT) {       // the tiled backward reads the forward's output
     TORCH_CHECK(out.has_value(), "attention_bwd: T > 64 needs the forward's out [B, T, E]");
     check_dev(*out, "out");
@@ -1911,9 +1913,9 @@ TORCH_LIBRARY(tdfo, m) {
         "Tensor(b!) part, Tensor(c!) grad, Tensor? gidx, bool defer=False) -> ()");
   m.def("encoder_reduce_flush() -> ()", encoder_reduce_flush);
   m.def("attention_fwd(Tensor qkv, Tensor ids, int H, float rate, int seed, Tensor? step, int pad_id, "
-        "Tensor(a!) out, Tensor(b!)? lse=None) -> ()");
+        "Tensor(a!) out, Tensor(b!)? lse=None, bool causal=False) -> ()");
   m.def("attention_bwd(Tensor qkv, Tensor ids, Tensor dout, int H, float rate, int seed, Tensor? step, "
-        "int pad_id, Tensor(a!) dqkv, Tensor? out=None, Tensor? lse=None) -> ()");
+        "int pad_id, Tensor(a!) dqkv, Tensor? out=None, Tensor? lse=None, bool causal=False) -> ()");
   m.def("layernorm_fwd(Tensor x, int n, float eps, Tensor gamma, Tensor beta, Tensor(a!) y, "
         "Tensor(b!) mean, Tensor(c!) rstd) -> ()");
   m.def("layernorm_bwd(Tensor x, Tensor g, int n, Tensor gamma, Tensor mean, Tensor rstd, "

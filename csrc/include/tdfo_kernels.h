@@ -507,6 +507,12 @@ struct AttnArgs {
   const float* dout; float* out; float* dqkv;
   int B, T, H, dk; float scale, rate; int64_t seed; const int64_t* step; int64_t pad_id;
   float* lse = nullptr;        // [B,H,T] row log-sum-exp, long-T path only (fwd writes, bwd reads)
+  // causal: query i sees keys j <= i only. A future key is excluded (P exactly
+  // 0, not counted in the row sum: a row whose visible keys are all PAD is
+  // uniform over its i + 1 keys); padded keys j <= i keep masked_fill(-1e9).
+  // The dropout hash keeps its keys, so the mask is the non-causal one
+  // restricted to j <= i.
+  int causal = 0;
 };
 // T <= 64: attention.hip (one wave per (sample, head)); 64 < T <= 512: the
 // tiled kernels below, which also need lse (and, backward, the forward's out).

@@ -15,6 +15,10 @@
 //             dV = P~^T dO from the LDS copies of P~ and dS.
 // qkv: [B, T, 3E] fp32 = the fused QKV Linear output (q | k | v, each
 // H x d_k), out/dout: [B, T, E]; dqkv: [B, T, 3E]. T <= 64, d_k <= 64.
+// CAUSAL: query i sees keys j <= i only (AttnArgs::causal). The query-phase
+// loops stop at j = i, so a future key is in no max, sum or product; the key
+// phase (lane = j) sums over queries i >= j and never reads pt / dsm above the
+// diagonal. The non-causal instantiations are the code they were.
 #include "tdfo_common.h"
 #include "tdfo_kernels.h"
 
@@ -52,7 +56,7 @@ __device__ __forceinline__ void stage_kv(const AttnArgs& a, int b, int h, float*
   }
 }
 
-template <int DK>
+template <int DK, bool CAUSAL>
 __global__ __launch_bounds__(64) void attn_fwd_kernel(AttnArgs a) {
   __shared__ float ks[AT_MAXT * AT_MAXDK], vs[AT_MAXT * AT_MAXDK];
   __shared__ int kvalid[AT_MAXT];
@@ -69,15 +73,16 @@ __global__ __launch_bounds__(64) void attn_fwd_kernel(AttnArgs a) {
   float q[DK];
   const float* qp = a.qkv + ((int64_t)b * T + i) * 3 * E + h * dk;
   _Pragma("unroll") for (int d = 0; d < dk; ++d) q[d] = qp[d] * a.scale;
+  const int jend = CAUSAL ? i + 1 : T;         // keys this query sees
   float mx = -3.0e38f;
-  for (int j = 0; j < T; ++j) {
+  for (int j = 0; j < jend; ++j) {
     float s = 0.f;
     _Pragma("unroll") for (int d = 0; d < dk; ++d) s += q[d] * ks[j * dk + d];
     s = kvalid[j] ? s : -1e9f;
     mx = fmaxf(mx, s);
   }
   float sum = 0.f;
-  for (int j = 0; j < T; ++j) {
+  for (int j = 0; j < jend; ++j) {
     float s = 0.f;
     _Pragma("unroll") for (int d = 0; d < dk; ++d) s += q[d] * ks[j * dk + d];
     s = kvalid[j] ? s : -1e9f;
@@ -86,7 +91,7 @@ __global__ __launch_bounds__(64) void attn_fwd_kernel(AttnArgs a) {
   const float inv = 1.f / sum, kscale = 1.f / (1.f - a.rate);
   float o[DK];
   _Pragma("unroll") for (int d = 0; d < dk; ++d) o[d] = 0.f;
-  for (int j = 0; j < T; ++j) {
+  for (int j = 0; j < jend; ++j) {
     float s = 0.f;
     _Pragma("unroll") for (int d = 0; d < dk; ++d) s += q[d] * ks[j * dk + d];
     s = kvalid[j] ? s : -1e9f;
@@ -98,7 +103,7 @@ __global__ __launch_bounds__(64) void attn_fwd_kernel(AttnArgs a) {
   _Pragma("unroll") for (int d = 0; d < dk; ++d) op[d] = o[d];
 }
 
-template <int DK>
+template <int DK, bool CAUSAL>
 __global__ __launch_bounds__(64) void attn_bwd_kernel(AttnArgs a) {
   __shared__ float ks[AT_MAXT * AT_MAXDK], vs[AT_MAXT * AT_MAXDK];
   __shared__ float qs[AT_MAXT * AT_MAXDK], dos[AT_MAXT * AT_MAXDK];
@@ -120,15 +125,16 @@ __global__ __launch_bounds__(64) void attn_bwd_kernel(AttnArgs a) {
   const float kscale = 1.f / (1.f - a.rate);
   if (lane < T) {
     const int i = lane;
+    const int jend = CAUSAL ? i + 1 : T;       // keys this query sees
     float mx = -3.0e38f;
-    for (int j = 0; j < T; ++j) {
+    for (int j = 0; j < jend; ++j) {
       float s = 0.f;
       _Pragma("unroll") for (int d = 0; d < dk; ++d) s += qs[i * dk + d] * ks[j * dk + d];
       s = kvalid[j] ? s : -1e9f;
       mx = fmaxf(mx, s);
     }
     float sum = 0.f;
-    for (int j = 0; j < T; ++j) {
+    for (int j = 0; j < jend; ++j) {
       float s = 0.f;
       _Pragma("unroll") for (int d = 0; d < dk; ++d) s += qs[i * dk + d] * ks[j * dk + d];
       s = kvalid[j] ? s : -1e9f;
@@ -137,7 +143,7 @@ __global__ __launch_bounds__(64) void attn_bwd_kernel(AttnArgs a) {
     const float inv = 1.f / sum;
     // P row, dP (through the dropout mask), rowsum(P * dP)
     float rs = 0.f;
-    for (int j = 0; j < T; ++j) {
+    for (int j = 0; j < jend; ++j) {
       float s = 0.f;
       _Pragma("unroll") for (int d = 0; d < dk; ++d) s += qs[i * dk + d] * ks[j * dk + d];
       s = kvalid[j] ? s : -1e9f;
@@ -153,7 +159,7 @@ __global__ __launch_bounds__(64) void attn_bwd_kernel(AttnArgs a) {
     // dS = P * (dP - rs); masked keys get no gradient (masked_fill)
     float dq[DK];
     _Pragma("unroll") for (int d = 0; d < dk; ++d) dq[d] = 0.f;
-    for (int j = 0; j < T; ++j) {
+    for (int j = 0; j < jend; ++j) {
       float s = 0.f;
       _Pragma("unroll") for (int d = 0; d < dk; ++d) s += qs[i * dk + d] * ks[j * dk + d];
       s = kvalid[j] ? s : -1e9f;
@@ -170,7 +176,7 @@ __global__ __launch_bounds__(64) void attn_bwd_kernel(AttnArgs a) {
     const int j = lane;
     float dkk[DK], dv[DK];
     _Pragma("unroll") for (int d = 0; d < dk; ++d) { dkk[d] = 0.f; dv[d] = 0.f; }
-    for (int i = 0; i < T; ++i) {
+    for (int i = CAUSAL ? j : 0; i < T; ++i) {      // (queries that see key j)
       const float ds = dsm[i * AT_MAXT + j], p = pt[i * AT_MAXT + j];
       _Pragma("unroll") for (int d = 0; d < dk; ++d) {
         dkk[d] += ds * qs[i * dk + d];     // qs already carries 1/sqrt(dk)
@@ -187,14 +193,18 @@ __global__ __launch_bounds__(64) void attn_bwd_kernel(AttnArgs a) {
 
 }  // namespace
 
+#define TDFO_ATTN_LAUNCH(KERNEL, DK)                                                       \
+  if (a.causal) hipLaunchKernelGGL((KERNEL<DK, true>), dim3(a.B * a.H), dim3(64), 0, s, a);  \
+  else hipLaunchKernelGGL((KERNEL<DK, false>), dim3(a.B * a.H), dim3(64), 0, s, a);          \
+  break;
 #define TDFO_ATTN_DISPATCH(KERNEL)                                               \
   switch (a.dk) {                                                                \
-    case 4: hipLaunchKernelGGL(KERNEL<4>, dim3(a.B * a.H), dim3(64), 0, s, a); break;   \
-    case 8: hipLaunchKernelGGL(KERNEL<8>, dim3(a.B * a.H), dim3(64), 0, s, a); break;   \
-    case 16: hipLaunchKernelGGL(KERNEL<16>, dim3(a.B * a.H), dim3(64), 0, s, a); break; \
-    case 32: hipLaunchKernelGGL(KERNEL<32>, dim3(a.B * a.H), dim3(64), 0, s, a); break; \
-    case 64: hipLaunchKernelGGL(KERNEL<64>, dim3(a.B * a.H), dim3(64), 0, s, a); break; \
-    default: throw std::runtime_error("attention: d_k must be 4/8/16/32/64");          \
+    case 4: TDFO_ATTN_LAUNCH(KERNEL, 4)                                          \
+    case 8: TDFO_ATTN_LAUNCH(KERNEL, 8)                                          \
+    case 16: TDFO_ATTN_LAUNCH(KERNEL, 16)                                        \
+    case 32: TDFO_ATTN_LAUNCH(KERNEL, 32)                                        \
+    case 64: TDFO_ATTN_LAUNCH(KERNEL, 64)                                        \
+    default: throw std::runtime_error("attention: d_k must be 4/8/16/32/64");    \
   }
 
 void attention_fwd(const AttnArgs& a, hipStream_t s) {
@@ -211,5 +221,6 @@ void attention_bwd(const AttnArgs& a, hipStream_t s) {
   TDFO_CHECK_HIP(hipGetLastError());
 }
 #undef TDFO_ATTN_DISPATCH
+#undef TDFO_ATTN_LAUNCH
 
 }  // namespace tdfo

@@ -4,7 +4,9 @@ stock eager torch with autograd on the same tensors and the same GPU. One JSON
 line per shape: forward + backward time of each (device events, alternating
 repeats, median / min / max), their ratio, the largest difference of outputs
 and gradients, and the HIP time's share of the f32-MFMA time of its algorithmic
-FLOPs (4 B H T^2 d_k forward + 10 B H T^2 d_k backward) at 155 TF."""
+FLOPs (4 B H T^2 d_k forward + 10 B H T^2 d_k backward) at 155 TF.
+--causal times the causal kernels (keys j <= i) against eager torch with the
+same combined mask; the FLOPs then count the T (T + 1) / 2 visible pairs."""
 import argparse
 import json
 import math
@@ -26,6 +28,7 @@ ap.add_argument("--rate", type=float, default=0.0, help="dropout rate of the HIP
 ap.add_argument("--iters", type=int, default=20, help="calls per timed window")
 ap.add_argument("--repeats", type=int, default=7)
 ap.add_argument("--no-torch", action="store_true")
+ap.add_argument("--causal", action="store_true", help="causal attention (keys j <= i)")
 args = ap.parse_args()
 assert torch.cuda.is_available(), "bench_attention needs a GPU"
 dev = "cuda"
@@ -53,10 +56,13 @@ for spec in args.shapes.split(","):
     step = torch.tensor([3], dtype=torch.int64, device=dev)
     out, dqkv = torch.empty(B, T, E, device=dev), torch.empty_like(qkv)
     lse = torch.empty(B, H, T, device=dev) if T > ops.ATTN_SHORT_MAXT else None
+    ckw = {"causal": True} if args.causal else {}
+    future = torch.ones(T, T, dtype=torch.bool, device=dev).triu(1)
 
     def hip():
-        ops.attention_fwd(qkv, ids, H, args.rate, 1, step, 0, out, lse=lse)
-        ops.attention_bwd(qkv, ids, dout, H, args.rate, 1, step, 0, dqkv, out=out, lse=lse)
+        ops.attention_fwd(qkv, ids, H, args.rate, 1, step, 0, out, lse=lse, **ckw)
+        ops.attention_bwd(qkv, ids, dout, H, args.rate, 1, step, 0, dqkv, out=out, lse=lse,
+                          **ckw)
 
     x = qkv.clone().requires_grad_(True)
     mask = (ids != 0).view(B, 1, 1, T)
@@ -66,6 +72,8 @@ for spec in args.shapes.split(","):
         x.grad = None
         q, k, v = x.view(B, T, 3, H, dk).permute(2, 0, 3, 1, 4)
         s = (q @ k.transpose(-2, -1) / math.sqrt(dk)).masked_fill(~mask, -1e9)
+        if args.causal:
+            s = s.masked_fill(future, float("-inf"))
         p = torch.dropout(torch.softmax(s, dim=-1), args.rate, True)
         o = (p @ v).transpose(1, 2).reshape(B, T, E)
         o.backward(dout)
@@ -80,12 +88,12 @@ for spec in args.shapes.split(","):
     for _ in range(args.repeats):                # alternate the two in one process
         for k, fn in fns.items():
             ms[k].append(window(fn, args.iters))
-    rec = {"B": B, "T": T, "E": E, "H": H, "d_k": dk, "rate": args.rate}
+    rec = {"B": B, "T": T, "E": E, "H": H, "d_k": dk, "rate": args.rate, "causal": args.causal}
     for k, v in ms.items():
         rec[f"{k}_ms"] = round(statistics.median(v), 4)
         rec[f"{k}_ms_min"] = round(min(v), 4)
         rec[f"{k}_ms_max"] = round(max(v), 4)
-    flops = 14.0 * B * H * T * T * dk
+    flops = 14.0 * B * H * (T * (T + 1) / 2 if args.causal else T * T) * dk
     rec["hip_fraction_of_f32_mfma_peak"] = round(flops / PEAK_F32_MFMA * 1e3 / rec["hip_ms"], 3)
     if not args.no_torch:
         rec["eager_over_hip"] = round(rec["eager_ms"] / rec["hip_ms"], 2)

@@ -3,7 +3,8 @@
 16, T=20, E=16, 2 heads, 2 layers) with a Goodreads-scale vocabulary.
 --max-len / --embed-dim / --heads / --layers pick another shape, e.g. the
 published BERT4Rec one: --max-len 200 --embed-dim 64 (T > 64 runs the tiled
-attention and wide LayerNorm kernels; the fused block covers T <= 64)."""
+attention and wide LayerNorm kernels; the fused block covers T <= 64).
+--causal trains the next-item (causal attention) model on shifted labels."""
 import argparse
 import json
 import sys
@@ -27,6 +28,8 @@ def main():
     ap.add_argument("--heads", type=int, default=2)
     ap.add_argument("--layers", type=int, default=2)
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--causal", action="store_true",
+                    help="causal attention, per-position input block, labels = the next item")
     ap.add_argument("--torch-encoder", action="store_true",
                     help="torch reference attention/LayerNorm instead of the HIP kernels")
     a = ap.parse_args()
@@ -35,10 +38,15 @@ def main():
         m.USE_FUSED = False
     dev = "cuda"
     T = a.max_len
-    tr = Bert4RecTrainer(a.items, T, a.embed_dim, a.heads, a.layers, a.batch, device=dev)
+    ckw = {"causal": True} if a.causal else {}
+    tr = Bert4RecTrainer(a.items, T, a.embed_dim, a.heads, a.layers, a.batch, device=dev, **ckw)
     g = torch.Generator(device=dev).manual_seed(0)
     pool = []
     for _ in range(8):
+        if a.causal:                 # windows of T + 1 items: inputs | the next item
+            w = torch.randint(1, a.items + 1, (a.batch, T + 1), device=dev, generator=g)
+            pool.append((w[:, :-1].contiguous(), w[:, 1:].contiguous()))
+            continue
         s = torch.randint(1, a.items + 1, (a.batch, T), device=dev, generator=g)
         m = torch.rand(a.batch, T, device=dev, generator=g) < 0.2
         m[:, -1] = True
@@ -59,7 +67,7 @@ def main():
     el = time.perf_counter() - t
     print(json.dumps({"model": "bert4rec", "batch": a.batch, "vocab": a.items + 2,
                       "max_len": T, "embed_dim": a.embed_dim, "heads": a.heads,
-                      "layers": a.layers,
+                      "layers": a.layers, "causal": a.causal,
                       "graph": not a.no_graph, "fused_encoder": not a.torch_encoder, "ms_per_step": round(el / a.steps * 1e3, 4),
                       "sequences_per_sec": round(a.batch * a.steps / el, 1),
                       "loss": round(tr.pop_loss(), 4)}))

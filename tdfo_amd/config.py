@@ -70,6 +70,7 @@ class Config:
     sliding_step: int = 10
     mask_prob: float = 0.2
     model_parallel: bool = False
+    objective: str = "masked"         # bert4rec: masked (BERT4Rec) | next_item (causal, SASRec-style)
     # derived
     size_map: Dict[str, int] = field(default_factory=dict)
     # ---- new (optional) keys
@@ -158,6 +159,10 @@ def validate(cfg: Config) -> None:
         raise ValueError("embed_dim and batch sizes must be positive")
     if cfg.model not in ("two_tower", "bert4rec", "dlrm", "dcnv2"):
         raise ValueError(f"unknown model {cfg.model!r}")
+    if cfg.objective not in ("masked", "next_item"):
+        raise ValueError(f"objective must be masked|next_item, got {cfg.objective!r}")
+    if cfg.objective == "next_item" and cfg.model != "bert4rec":
+        raise ValueError("objective = next_item is supported by the bert4rec model only")
     if cfg.table_dtype not in ("fp32", "bf16"):
         raise ValueError(f"table_dtype must be fp32|bf16, got {cfg.table_dtype!r}")
     if cfg.table_dtype == "bf16" and cfg.model not in ("dlrm", "dcnv2"):
@@ -178,8 +183,11 @@ def read_configs(path: Optional[Path | str] = None, overrides: Sequence[str] = (
         cand = (base / cfg.data_dir)
         cfg.data_dir = cand if cand.exists() or not cfg.data_dir.exists() else cfg.data_dir.absolute()
     if size_map:
-        for name in ("size_map.json", "size_map_bert4rec.json"):
-            fname = "size_map_bert4rec.json" if cfg.model == "bert4rec" else "size_map.json"
+        for name in ("size_map.json", "size_map_bert4rec.json", "size_map_sasrec.json"):
+            fname = "size_map.json"
+            if cfg.model == "bert4rec":
+                fname = ("size_map_sasrec.json" if cfg.objective == "next_item"
+                         else "size_map_bert4rec.json")
             if name != fname:
                 continue
             p = cfg.data_dir / name

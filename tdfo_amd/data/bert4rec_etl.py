@@ -15,6 +15,14 @@
     negatives (the reference's set difference can come up short);
   * FILE_NUM=2 parquet parts with list<int32> columns, train parts shuffled
     with seed 42; ``size_map_bert4rec.json {n_users, n_items}`` (:318-375).
+
+``objective="next_item"`` (causal / SASRec-style training) writes
+``parquet_sasrec/`` and ``size_map_sasrec.json`` with the same column names:
+training windows of ``max_len + 1`` raw train items every ``sliding_step``,
+``train_interactions = w[:, :-1]``, ``labels = w[:, 1:]`` (the next item, PAD
+past the end; no MASK token, no RNG); eval sequences are the last ``max_len``
+train items left-padded, with no MASK slot. The vocabulary keeps its
+``n_items + 2`` rows so table shapes match the masked model's.
 """
 from __future__ import annotations
 
@@ -108,6 +116,29 @@ def sliding_windows(seq, lens, seq_len, step):
     return user_of, out
 
 
+def next_item_windows(b, starts, train_len, seq_len, step):
+    """Next-item training windows: (user index, inputs [n, seq_len], labels
+    [n, seq_len]) with labels[:, t] = the item after inputs[:, t] (PAD at and
+    after a user's last train item)."""
+    idx = np.concatenate([np.arange(s, s + L) for s, L in zip(starts, train_len)])
+    user_of, w = sliding_windows(b[idx], train_len, seq_len + 1, step)
+    return user_of, np.ascontiguousarray(w[:, :-1]), np.ascontiguousarray(w[:, 1:])
+
+
+def eval_seqs_next_item(b, starts, train_len, seq_len):
+    """Last seq_len train items per user, left-padded (the last position's
+    hidden state is the next-item query: no MASK slot)."""
+    n = len(train_len)
+    out = np.full((n, seq_len), PAD_ID, dtype=np.int32)
+    take = np.minimum(train_len, seq_len)
+    for i in range(n):
+        k = take[i]
+        if k:
+            s = starts[i] + train_len[i] - k
+            out[i, seq_len - k:] = b[s: s + k]
+    return out
+
+
 def eval_seqs(b, starts, train_len, seq_len, mask_id):
     n = len(train_len)
     out = np.full((n, seq_len), PAD_ID, dtype=np.int32)
@@ -168,9 +199,43 @@ def _write_parts(write_dir: Path, cols: Dict[str, np.ndarray], prefix: str, verb
             print(f"{prefix} part_{i} finished in {(time.perf_counter() - t0):.2f}s")
 
 
+OBJECTIVES = ("masked", "next_item")
+
+
+def _run_etl_next_item(data_dir: Path, max_len: int, sliding_step: int, seed: int, verbose: bool):
+    user, book = read_sorted(data_dir)
+    if verbose:
+        print(f"data size: {len(user):,}")
+    u, b, n_users, n_items = map_ids(user, book)
+    items, probs = item_popularity(b)
+    (data_dir / "size_map_sasrec.json").write_text(
+        json.dumps({"n_users": n_users, "n_items": n_items}, indent=4))
+    starts, train_len, eval_item = split(u, b)
+    uidx, seqs, labs = next_item_windows(b, starts, train_len, max_len, sliding_step)
+    train = {"user_id": (uidx + 1).astype(np.int32), "train_interactions": seqs, "labels": labs}
+    if verbose:
+        print(f"train seq data size: {len(seqs):,}")
+    out = data_dir / "parquet_sasrec"
+    _write_parts(out, train, "train", verbose)
+    ev = eval_seqs_next_item(b, starts, train_len, max_len)
+    negs = sample_negatives(b, starts, train_len, eval_item, items, probs,
+                            np.random.default_rng(seed))
+    cand = np.concatenate([eval_item[:, None].astype(np.int32), negs], 1)
+    evald = {"user_id": np.arange(1, n_users + 1, dtype=np.int32), "eval_seqs": ev,
+             "candidate_items": cand}
+    if verbose:
+        print(f"eval seq data size: {len(ev):,}")
+    _write_parts(out, evald, "eval", verbose)
+    return {"n_users": n_users, "n_items": n_items, "n_train_seqs": len(seqs)}
+
+
 def run_etl(data_dir, max_len: int = 20, sliding_step: int = 10, mask_prob: float = 0.2,
-            seed: int = 42, verbose: bool = True):
+            seed: int = 42, verbose: bool = True, objective: str = "masked"):
     data_dir = Path(data_dir)
+    if objective not in OBJECTIVES:
+        raise ValueError(f"objective must be one of {OBJECTIVES}, got {objective!r}")
+    if objective == "next_item":
+        return _run_etl_next_item(data_dir, max_len, sliding_step, seed, verbose)
     rng = np.random.default_rng(seed)
     user, book = read_sorted(data_dir)
     if verbose:

@@ -22,6 +22,14 @@ What is different on MI355X:
     launch (torch.optim.Adam semantics: L2 weight decay added to the grad);
   * the whole single-GPU step (encoder fwd/bwd included) is captured into
     one hipGraph (the encoder is ~100 tiny ops at E=16, T=20).
+
+``causal=True`` is the next-item (SASRec-style, full-softmax CE) sibling: the
+same encoder, item table and output layer, attention restricted to keys
+j <= i, and a per-position input block dropout(LayerNorm_E(item_emb + pos))
+(the joint [T, E] LayerNorm mixes statistics over positions and would leak
+the future). Labels are the next item at every position; PAD labels are
+ignored by the same fused Linear+CE. Causal models take the per-op path at
+every shape (encoder.hip's fused block has no causal form).
 """
 from __future__ import annotations
 
@@ -55,17 +63,19 @@ GPU_EMBED_DIMS = (16, 32, 64, 128, 256)   # ops.linear_xent's kernels (output la
 GPU_MAX_ROW = 32768                       # joint [T, E] LayerNorm / input block row
 
 
-def check_gpu_shape(max_len: int, embed_dim: int, n_heads: int) -> None:
+def check_gpu_shape(max_len: int, embed_dim: int, n_heads: int, causal: bool = False) -> None:
     """Raise ValueError unless the GPU kernels cover this Bert4Rec shape (the
-    CPU path has no such limits)."""
+    CPU path has no such limits). A causal model has no joint [T, E] row, so
+    max_len * embed_dim is not limited there."""
     ok = (embed_dim in GPU_EMBED_DIMS and n_heads > 0 and embed_dim % n_heads == 0
           and embed_dim // n_heads in ops.ATTN_DK and 0 < max_len <= ops.ATTN_LONG_MAXT
-          and max_len * embed_dim <= GPU_MAX_ROW)
+          and (causal or max_len * embed_dim <= GPU_MAX_ROW))
     if not ok:
+        row = "" if causal else f" and max_len * embed_dim <= {GPU_MAX_ROW}"
         raise ValueError(
             f"Bert4Rec on the GPU supports embed_dim in {GPU_EMBED_DIMS}, d_k = embed_dim / "
-            f"heads in {ops.ATTN_DK}, max_len <= {ops.ATTN_LONG_MAXT} and max_len * embed_dim <= "
-            f"{GPU_MAX_ROW}; got embed_dim = {embed_dim}, heads = {n_heads}, max_len = {max_len}")
+            f"heads in {ops.ATTN_DK}, max_len <= {ops.ATTN_LONG_MAXT}{row}; "
+            f"got embed_dim = {embed_dim}, heads = {n_heads}, max_len = {max_len}")
 # whole transformer block in one fwd / one bwd kernel (encoder.hip); False
 # keeps the per-op path (fused attention core + LayerNorm kernels, torch GEMMs)
 USE_FUSED_BLOCK = True
@@ -80,7 +90,7 @@ def _fused(x: torch.Tensor) -> bool:
 
 class _AttnCoreFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, ids, H, rate, seed, step):
+    def forward(ctx, qkv, ids, H, rate, seed, step, causal=False):
         qkv = qkv.contiguous()
         B, T, E3 = qkv.shape
         out = torch.empty(B, T, E3 // 3, dtype=qkv.dtype, device=qkv.device)
@@ -88,26 +98,27 @@ class _AttnCoreFn(torch.autograd.Function):
             # tiled kernels: the backward recomputes P from the saved row
             # log-sum-exp and takes rowsum(P o dP) from dO . O
             lse = torch.empty(B, H, T, dtype=torch.float32, device=qkv.device)
-            ops.attention_fwd(qkv, ids, H, rate, seed, step, PAD_ID, out, lse=lse)
+            ops.attention_fwd(qkv, ids, H, rate, seed, step, PAD_ID, out, lse=lse, causal=causal)
             ctx.save_for_backward(qkv, ids, step, out, lse)
         else:
-            ops.attention_fwd(qkv, ids, H, rate, seed, step, PAD_ID, out)
+            ops.attention_fwd(qkv, ids, H, rate, seed, step, PAD_ID, out, causal=causal)
             ctx.save_for_backward(qkv, ids, step)
-        ctx.cfg = (H, rate, seed)
+        ctx.cfg = (H, rate, seed, causal)
         return out
 
     @staticmethod
     def backward(ctx, g):
         qkv, ids, step = ctx.saved_tensors[:3]
-        H, rate, seed = ctx.cfg
+        H, rate, seed, causal = ctx.cfg
         dqkv = torch.empty_like(qkv)
         if len(ctx.saved_tensors) > 3:
             out, lse = ctx.saved_tensors[3:]
             ops.attention_bwd(qkv, ids, g.contiguous(), H, rate, seed, step, PAD_ID, dqkv,
-                              out=out, lse=lse)
+                              out=out, lse=lse, causal=causal)
         else:
-            ops.attention_bwd(qkv, ids, g.contiguous(), H, rate, seed, step, PAD_ID, dqkv)
-        return dqkv, None, None, None, None, None
+            ops.attention_bwd(qkv, ids, g.contiguous(), H, rate, seed, step, PAD_ID, dqkv,
+                              causal=causal)
+        return dqkv, None, None, None, None, None, None
 
 
 class _LayerNormFn(torch.autograd.Function):
@@ -251,10 +262,11 @@ def layer_norm(x: torch.Tensor, ln: nn.LayerNorm) -> torch.Tensor:
 
 class KeyPad:
     """Attention context of the fused path: item ids (key-padding mask is
-    ids != PAD) and the device step counter that keys the dropout hash."""
+    ids != PAD), the device step counter that keys the dropout hash, and
+    whether attention is causal (keys j <= i only)."""
 
-    def __init__(self, ids: torch.Tensor, step: Optional[torch.Tensor]):
-        self.ids, self.step = ids, step
+    def __init__(self, ids: torch.Tensor, step: Optional[torch.Tensor], causal: bool = False):
+        self.ids, self.step, self.causal = ids, step, causal
 
 
 # ------------------------------------------------------------------ encoder
@@ -268,6 +280,7 @@ class MultiHeadedAttention(nn.Module):
         self.output_linear = nn.Linear(dim, dim)
         self.dropout = nn.Dropout(dropout)
         self.seed = 0x5EED                 # per-layer dropout-hash seed (set by Bert4Rec)
+        self.causal = False                # torch branch's future-key mask (set by Bert4Rec)
 
     def forward(self, x, mask):
         B, T, _ = x.shape
@@ -276,12 +289,15 @@ class MultiHeadedAttention(nn.Module):
         if isinstance(mask, KeyPad):
             rate = self.dropout.p if self.training else 0.0
             core = _AttnCoreFn.apply(F.linear(x, w, b), mask.ids, self.h, rate, self.seed,
-                                     mask.step)
+                                     mask.step, mask.causal)
             return self.output_linear(core)
         qkv = F.linear(x, w, b).view(B, T, 3, self.h, self.d_k).permute(2, 0, 3, 1, 4)
         q, k, v = qkv[0], qkv[1], qkv[2]
         scores = torch.matmul(q, k.transpose(-2, -1)) / math.sqrt(self.d_k)
         scores = scores.masked_fill(~mask, -1e9)
+        if self.causal:                    # future keys excluded (after the padding fill)
+            future = torch.ones(T, T, dtype=torch.bool, device=x.device).triu(1)
+            scores = scores.masked_fill(future, float("-inf"))
         p = self.dropout(torch.softmax(scores, dim=-1))
         out = torch.matmul(p, v).transpose(1, 2).reshape(B, T, self.h * self.d_k)
         return self.output_linear(out)
@@ -329,7 +345,7 @@ class TransformerBlock(nn.Module):
 
     def forward(self, x, mask):
         att = self.attention
-        if (USE_FUSED_BLOCK and isinstance(mask, KeyPad) and x.is_cuda
+        if (USE_FUSED_BLOCK and isinstance(mask, KeyPad) and not mask.causal and x.is_cuda
                 and _fused_block_ok(x.shape[1], x.shape[2], att.h, self.feed_forward.w_1.out_features)):
             rate = self.dropout.p if self.training else 0.0
             return _EncoderLayerFn.apply(x, mask.ids, mask.step, att.h, rate, att.seed,
@@ -464,17 +480,20 @@ class Bert4Rec(nn.Module):
     torchrec's Bert4Rec except the item table, exported by the trainer)."""
 
     def __init__(self, vocab_size: int, max_len: int, embed_dim: int, num_heads: int,
-                 num_layers: int, dropout: float = 0.1):
+                 num_layers: int, dropout: float = 0.1, causal: bool = False):
         super().__init__()
         self.vocab_size, self.max_len, self.emb_dim = vocab_size, max_len, embed_dim
+        self.causal = bool(causal)
         self.positional_encoding = nn.Parameter(torch.randn(max_len, embed_dim))
-        self.layernorm = nn.LayerNorm([max_len, embed_dim])
+        # causal: per position (a joint [T, E] row would mix in the future)
+        self.layernorm = nn.LayerNorm(embed_dim if causal else [max_len, embed_dim])
         self.emb_dropout = nn.Dropout(dropout)
         self.transformer_blocks = nn.ModuleList(
             [TransformerBlock(embed_dim, num_heads, dropout) for _ in range(num_layers)])
         self.out = nn.Linear(embed_dim, vocab_size)
         for i, blk in enumerate(self.transformer_blocks):
             blk.attention.seed = 0x5EED + 7919 * i
+            blk.attention.causal = self.causal
         # device step counter for the fused attention's dropout hash (advanced
         # once per training step by the trainer, inside the captured graph)
         self.register_buffer("rng_step", torch.zeros(1, dtype=torch.int64), persistent=False)
@@ -482,10 +501,14 @@ class Bert4Rec(nn.Module):
     def encode(self, item_emb: torch.Tensor, seqs: torch.Tensor) -> torch.Tensor:
         """item_emb [B, T, E] (looked-up rows), seqs [B, T] ids -> hidden [B, T, E]."""
         if _fused(item_emb):
-            mask = KeyPad(seqs.contiguous(), self.rng_step)
+            mask = KeyPad(seqs.contiguous(), self.rng_step, self.causal)
         else:
             mask = (seqs != PAD_ID).unsqueeze(1).unsqueeze(1)      # [B, 1, 1, T] key mask
-        if _fused(item_emb):
+        if self.causal:
+            # per-position input block from the LayerNorm kernel (n = E) and
+            # nn.Dropout; the sequence prologue's LN is the joint one
+            x = self.emb_dropout(layer_norm(item_emb + self.positional_encoding, self.layernorm))
+        elif _fused(item_emb):
             rate = self.emb_dropout.p if self.training else 0.0
             x = _SeqPrologueFn.apply(item_emb, self.positional_encoding, self.layernorm.weight,
                                      self.layernorm.bias, self.layernorm.eps, rate,
@@ -495,6 +518,18 @@ class Bert4Rec(nn.Module):
         for blk in self.transformer_blocks:
             x = blk(x, mask)
         return x
+
+
+    def load_state_dict(self, state_dict, *args, **kwargs):
+        # the input LayerNorm is [E] in a causal model and [T, E] otherwise
+        w = state_dict.get("layernorm.weight") if hasattr(state_dict, "get") else None
+        if w is not None and tuple(w.shape) != tuple(self.layernorm.weight.shape):
+            kind = lambda c: "causal (next-item)" if c else "non-causal (masked-item)"
+            raise ValueError(
+                f"checkpoint is of a {kind(w.dim() == 1)} model (layernorm.weight "
+                f"{tuple(w.shape)}) and cannot be loaded into this {kind(self.causal)} model "
+                f"(layernorm.weight {tuple(self.layernorm.weight.shape)})")
+        return super().load_state_dict(state_dict, *args, **kwargs)
 
 
 # ------------------------------------------------------------------ metrics
@@ -524,16 +559,19 @@ class Bert4RecTrainer:
     def __init__(self, n_items: int, max_len: int = 20, embed_dim: int = 16, n_heads: int = 2,
                  n_layers: int = 2, batch_size: int = 16, lr: float = 3e-4, wd: float = 1e-4,
                  device="cpu", mode: str = "local", group=None, rank: int = 0, world: int = 1,
-                 dropout: float = 0.1, seed: int = 42, label_smoothing: float = 0.1):
+                 dropout: float = 0.1, seed: int = 42, label_smoothing: float = 0.1,
+                 causal: bool = False):
         self.V = n_items + 2                     # 0 = PAD, n_items + 1 = MASK
         self.T, self.E, self.B = max_len, embed_dim, batch_size
+        self.causal = bool(causal)               # next-item objective (module docstring)
         self.device = dev = torch.device(device)
         if dev.type == "cuda":
-            check_gpu_shape(max_len, embed_dim, n_heads)
+            check_gpu_shape(max_len, embed_dim, n_heads, self.causal)
         self.mode, self.group, self.rank, self.world = mode, group, rank, world
         self.eps = label_smoothing
         torch.manual_seed(seed)
-        self.model = Bert4Rec(self.V, max_len, embed_dim, n_heads, n_layers, dropout).to(dev)
+        self.model = Bert4Rec(self.V, max_len, embed_dim, n_heads, n_layers, dropout,
+                              causal=self.causal).to(dev)
         emb_opt = EmbOptimConfig("adam", lr=lr, weight_decay=wd)
         ntok = batch_size * max_len
         if mode == "dmp":
@@ -573,7 +611,10 @@ class Bert4RecTrainer:
         # flat views), so autograd accumulates nothing there (the QKV cat's
         # backward and 35 AccumulateGrad adds per step before)
         self._zero_ranges = None
-        if dev.type == "cuda" and os.environ.get("TDFO_B4R_DIRECT_GRADS", "1") != "0":
+        # (a causal model runs neither the fused prologue nor the fused block:
+        # autograd accumulates every gradient, and a step zeroes them all)
+        if (dev.type == "cuda" and not self.causal
+                and os.environ.get("TDFO_B4R_DIRECT_GRADS", "1") != "0"):
             self._attach_direct_grads()
         self.seqs = torch.zeros(batch_size, max_len, dtype=torch.int64, device=dev)
         self.labels = torch.zeros(batch_size, max_len, dtype=torch.int64, device=dev)
@@ -634,7 +675,9 @@ class Bert4RecTrainer:
     def _zero_grads(self):
         m = self.model
         ff = m.transformer_blocks[0].feed_forward.w_1.out_features if len(m.transformer_blocks) else 0
-        direct = (self._zero_ranges is not None and USE_FUSED and USE_FUSED_BLOCK and
+        # (causal: the per-op path only, whose gradients autograd accumulates)
+        direct = (self._zero_ranges is not None and not self.causal and USE_FUSED and
+                  USE_FUSED_BLOCK and
                   _fused_block_ok(self.T, self.E, m.transformer_blocks[0].attention.h, ff)
                   if len(m.transformer_blocks) else False)
         if not direct:
@@ -845,3 +888,29 @@ class Bert4RecTrainer:
         if self.mode == "ddp":
             sd = {"module." + k: v for k, v in sd.items()}
         return sd
+
+    def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
+        """Inverse of state_dict(): dense parameters and the item table. A
+        checkpoint of the other objective (causal / non-causal) is refused
+        with a ValueError naming both."""
+        table_key = "history.embed_collection.embeddings.item_embedding.weight"
+        dense = {}
+        table = None
+        for k, v in sd.items():
+            k = k[len("module."):] if k.startswith("module.") else k
+            if k == table_key:
+                table = v
+            elif k.startswith("history."):
+                dense[k[len("history."):]] = v
+            else:
+                dense[k] = v
+        self.model.load_state_dict(dense)
+        if table is None or tuple(table.shape) != (self.V, self.E):
+            raise ValueError(f"checkpoint item table must be [{self.V}, {self.E}], got "
+                             f"{None if table is None else tuple(table.shape)}")
+        table = table.to(self.device, torch.float32)
+        if self.mode == "dmp":
+            self.item.set_table_weight(0, table)
+        else:
+            with torch.no_grad():
+                self.item.weight[: self.V].copy_(table)

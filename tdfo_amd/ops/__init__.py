@@ -954,29 +954,33 @@ def _attn_gpu_check(qkv, H, need, have):
                          f"need {need}")
 
 
-def attention_fwd(qkv, ids, H, rate, seed, step, pad_id, out, lse=None):
+def attention_fwd(qkv, ids, H, rate, seed, step, pad_id, out, lse=None, causal=False):
     """Fused MHA core: qkv [B,T,3E] fp32 -> out [B,T,E] (key-padding mask from
     ids != pad_id, hash dropout keyed by (seed, step[0])). On the GPU T <= 64
     runs one wave per (sample, head) and ignores ``lse``; 64 < T <= 512 runs
     the tiled kernels, which write the row log-sum-exp into ``lse``
-    (fp32 [B, H, T], required there) for the backward."""
+    (fp32 [B, H, T], required there) for the backward. ``causal``: query i
+    sees keys j <= i only (future keys excluded, padded visible keys still
+    masked_fill(-1e9); the dropout mask is the non-causal one restricted to
+    j <= i)."""
     if _gpu(qkv):
         _attn_gpu_check(qkv, H, "lse (fp32 [B, H, T])", (lse,))
         _native().attention_fwd(qkv, ids, int(H), float(rate), int(seed), step, int(pad_id), out,
-                                lse)
+                                lse, bool(causal))
     else:
-        ref.attention_fwd(qkv, ids, H, rate, seed, step, pad_id, out)
+        ref.attention_fwd(qkv, ids, H, rate, seed, step, pad_id, out, causal=causal)
 
 
-def attention_bwd(qkv, ids, dout, H, rate, seed, step, pad_id, dqkv, out=None, lse=None):
+def attention_bwd(qkv, ids, dout, H, rate, seed, step, pad_id, dqkv, out=None, lse=None,
+                  causal=False):
     """dqkv of attention_fwd. 64 < T <= 512 on the GPU needs the forward's
     ``out`` and ``lse``; both are ignored for T <= 64 and on the CPU."""
     if _gpu(qkv):
         _attn_gpu_check(qkv, H, "the forward's out and lse", (out, lse))
         _native().attention_bwd(qkv, ids, dout, int(H), float(rate), int(seed), step,
-                                int(pad_id), dqkv, out, lse)
+                                int(pad_id), dqkv, out, lse, bool(causal))
     else:
-        ref.attention_bwd(qkv, ids, dout, H, rate, seed, step, pad_id, dqkv)
+        ref.attention_bwd(qkv, ids, dout, H, rate, seed, step, pad_id, dqkv, causal=causal)
 
 
 LN_NARROW_MAXN = 1024      # wider rows (to 32768) take the one-workgroup-per-row path

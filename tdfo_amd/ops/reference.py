@@ -697,8 +697,11 @@ def attn_keep_scale(B: int, H: int, T: int, rate: float, seed: int, step: int, d
     return keep.to(torch.float32) / (1.0 - rate)
 
 
-def attention_core(qkv, ids, H, rate, seed, step, pad_id):
-    """Differentiable torch reference of the fused kernel: qkv [B,T,3E] -> [B,T,E]."""
+def attention_core(qkv, ids, H, rate, seed, step, pad_id, causal=False):
+    """Differentiable torch reference of the fused kernel: qkv [B,T,3E] -> [B,T,E].
+    causal: after the key-padding masked_fill(-1e9), keys j > i are filled with
+    -inf (excluded: a row whose visible keys are all PAD is uniform over its
+    i + 1 keys); the dropout multiplier is the same [B, H, T, T] hash."""
     B, T, E3 = qkv.shape
     E = E3 // 3
     dk = E // H
@@ -706,20 +709,23 @@ def attention_core(qkv, ids, H, rate, seed, step, pad_id):
     s = (q / math.sqrt(dk)) @ k.transpose(-2, -1)
     mask = (ids != pad_id).view(B, 1, 1, T)
     s = s.masked_fill(~mask, -1e9)
+    if causal:
+        future = torch.ones(T, T, dtype=torch.bool, device=qkv.device).triu(1)
+        s = s.masked_fill(future, float("-inf"))
     p = torch.softmax(s, dim=-1) * attn_keep_scale(B, H, T, rate, seed, step, qkv.device)
     return (p @ v).transpose(1, 2).reshape(B, T, E)
 
 
-def attention_fwd(qkv, ids, H, rate, seed, step, pad_id, out):
+def attention_fwd(qkv, ids, H, rate, seed, step, pad_id, out, causal=False):
     out.copy_(attention_core(qkv, ids, H, rate, seed, int(step[0]) if step is not None else 0,
-                             pad_id))
+                             pad_id, causal=causal))
 
 
-def attention_bwd(qkv, ids, dout, H, rate, seed, step, pad_id, dqkv):
+def attention_bwd(qkv, ids, dout, H, rate, seed, step, pad_id, dqkv, causal=False):
     x = qkv.detach().requires_grad_(True)
     with torch.enable_grad():
         o = attention_core(x, ids, H, rate, seed, int(step[0]) if step is not None else 0,
-                           pad_id)
+                           pad_id, causal=causal)
         (g,) = torch.autograd.grad(o, x, dout)
     dqkv.copy_(g)
 

@@ -47,14 +47,17 @@ def run(cfg: Config, out_dir: str = ".", device: Optional[str] = None) -> List[D
     info = init_distributed(device)
     guarded.rank_preflight(info)          # W > 1: collective self-test, c10d on mismatch
     rank, world, dev, group = info.rank, info.world_size, info.device, info.group
-    root = cfg.data_dir / "parquet_bert4rec"
+    # objective = next_item: the causal model on the next-item ETL output
+    causal = cfg.objective == "next_item"
+    root = cfg.data_dir / ("parquet_sasrec" if causal else "parquet_bert4rec")
     train_cols = read_columns(str(root / cfg.train_data))
     eval_cols = read_columns(str(root / cfg.eval_data))
     n_tr, n_ev = len(train_cols["user_id"]), len(eval_cols["user_id"])
     if rank == 0:
         print(f"===== train size: {n_tr:,}, eval size: {n_ev:,} =====")
         print(f"===== num devices: {world} =====\n")
-    sm = cfg.size_map or json.loads((cfg.data_dir / "size_map_bert4rec.json").read_text())
+    sm_name = "size_map_sasrec.json" if causal else "size_map_bert4rec.json"
+    sm = cfg.size_map or json.loads((cfg.data_dir / sm_name).read_text())
     n_items = int(sm["n_items"])
     if rank == 0:
         print(f"==== vocab size: {n_items + 2:,} ====")
@@ -62,7 +65,7 @@ def run(cfg: Config, out_dir: str = ".", device: Optional[str] = None) -> List[D
     B, EB = cfg.per_device_train_batch_size, cfg.per_device_eval_batch_size
     tr = Bert4RecTrainer(n_items, cfg.max_len, cfg.embed_dim, cfg.n_heads, cfg.n_layers, B,
                          cfg.learning_rate, cfg.weight_decay, dev, mode, group, rank, world,
-                         seed=cfg.seed)
+                         seed=cfg.seed, causal=causal)
     data_dev = dev if cfg.data_on_device else torch.device("cpu")
     train = DeviceColumns({"seqs": train_cols["train_interactions"].astype("int64"),
                            "labels": train_cols["labels"].astype("int64")}, data_dev)
