@@ -44,6 +44,25 @@ __device__ __forceinline__ bool keep(const AttnArgs& a, int b, int h, int i, int
   return (float)(r >> 8) * (1.0f / 16777216.0f) >= a.rate;
 }
 
+// Score q . k of one (query, key) pair. Every pass of a kernel recomputes the
+// scores, and the row maximum must be one of the values the later passes
+// subtract it from, bit for bit: explicit fmaf, because with `s += q * k` the
+// compiler contracted the (two-keys-at-a-time) maximum pass into FMAs and left
+// the exponent passes as multiplies and adds. Then s - max != 0 at the maximum
+// and P there is 1 +- an ulp of the score: a row with one valid key (P one-hot,
+// dS = 0) leaked ~1e-6 into dQ and that key's dK
+// (profiles/encoder_oracle.md). Any rounding change here moves the trainer
+// tests that compare a step with the CPU at hidden 128 / 256: Adam divides
+// near-zero gradients by their own size (tests/test_gpu_bert4rec_wide.py).
+// Of the equivalent chain orders tried, this one keeps all of them inside
+// their tolerances; keep it unless those tests are re-measured.
+template <int DK>
+__device__ __forceinline__ float qk_dot(const float* q, const float* k) {
+  float s[4] = {0.f, 0.f, 0.f, 0.f};     // 4 independent chains
+  _Pragma("unroll") for (int d = 0; d < DK; ++d) s[d & 3] = fmaf(q[d], k[d], s[d & 3]);
+  return (s[0] + s[2]) + (s[1] + s[3]);
+}
+
 // Fill LDS with this (b, h)'s K and V rows: [T][dk] each.
 __device__ __forceinline__ void stage_kv(const AttnArgs& a, int b, int h, float* ks, float* vs,
                                          int lane) {
@@ -76,15 +95,13 @@ __global__ __launch_bounds__(64) void attn_fwd_kernel(AttnArgs a) {
   const int jend = CAUSAL ? i + 1 : T;         // keys this query sees
   float mx = -3.0e38f;
   for (int j = 0; j < jend; ++j) {
-    float s = 0.f;
-    _Pragma("unroll") for (int d = 0; d < dk; ++d) s += q[d] * ks[j * dk + d];
+    float s = qk_dot<DK>(q, ks + j * dk);
     s = kvalid[j] ? s : -1e9f;
     mx = fmaxf(mx, s);
   }
   float sum = 0.f;
   for (int j = 0; j < jend; ++j) {
-    float s = 0.f;
-    _Pragma("unroll") for (int d = 0; d < dk; ++d) s += q[d] * ks[j * dk + d];
+    float s = qk_dot<DK>(q, ks + j * dk);
     s = kvalid[j] ? s : -1e9f;
     sum += __expf(s - mx);
   }
@@ -92,8 +109,7 @@ __global__ __launch_bounds__(64) void attn_fwd_kernel(AttnArgs a) {
   float o[DK];
   _Pragma("unroll") for (int d = 0; d < dk; ++d) o[d] = 0.f;
   for (int j = 0; j < jend; ++j) {
-    float s = 0.f;
-    _Pragma("unroll") for (int d = 0; d < dk; ++d) s += q[d] * ks[j * dk + d];
+    float s = qk_dot<DK>(q, ks + j * dk);
     s = kvalid[j] ? s : -1e9f;
     float p = __expf(s - mx) * inv;
     p = keep(a, b, h, i, j, step) ? p * kscale : 0.f;
@@ -128,15 +144,13 @@ __global__ __launch_bounds__(64) void attn_bwd_kernel(AttnArgs a) {
     const int jend = CAUSAL ? i + 1 : T;       // keys this query sees
     float mx = -3.0e38f;
     for (int j = 0; j < jend; ++j) {
-      float s = 0.f;
-      _Pragma("unroll") for (int d = 0; d < dk; ++d) s += qs[i * dk + d] * ks[j * dk + d];
+      float s = qk_dot<DK>(qs + i * dk, ks + j * dk);
       s = kvalid[j] ? s : -1e9f;
       mx = fmaxf(mx, s);
     }
     float sum = 0.f;
     for (int j = 0; j < jend; ++j) {
-      float s = 0.f;
-      _Pragma("unroll") for (int d = 0; d < dk; ++d) s += qs[i * dk + d] * ks[j * dk + d];
+      float s = qk_dot<DK>(qs + i * dk, ks + j * dk);
       s = kvalid[j] ? s : -1e9f;
       sum += __expf(s - mx);
     }
@@ -144,8 +158,7 @@ __global__ __launch_bounds__(64) void attn_bwd_kernel(AttnArgs a) {
     // P row, dP (through the dropout mask), rowsum(P * dP)
     float rs = 0.f;
     for (int j = 0; j < jend; ++j) {
-      float s = 0.f;
-      _Pragma("unroll") for (int d = 0; d < dk; ++d) s += qs[i * dk + d] * ks[j * dk + d];
+      float s = qk_dot<DK>(qs + i * dk, ks + j * dk);
       s = kvalid[j] ? s : -1e9f;
       const float p = __expf(s - mx) * inv;
       const float m = keep(a, b, h, i, j, step) ? kscale : 0.f;
@@ -160,8 +173,7 @@ __global__ __launch_bounds__(64) void attn_bwd_kernel(AttnArgs a) {
     float dq[DK];
     _Pragma("unroll") for (int d = 0; d < dk; ++d) dq[d] = 0.f;
     for (int j = 0; j < jend; ++j) {
-      float s = 0.f;
-      _Pragma("unroll") for (int d = 0; d < dk; ++d) s += qs[i * dk + d] * ks[j * dk + d];
+      float s = qk_dot<DK>(qs + i * dk, ks + j * dk);
       s = kvalid[j] ? s : -1e9f;
       const float pp = __expf(s - mx) * inv;
       const float ds = kvalid[j] ? pp * (dsm[i * AT_MAXT + j] - rs) : 0.f;

@@ -599,14 +599,16 @@ size_t bwd_smem(const EncArgs& a) {
 bool shape_ok(int E, int H) {
   if (H < 1 || E % H != 0) return false;
   const int dk = E / H;
-  return (E == 16 || E == 32 || E == 64) && (dk == 4 || dk == 8 || dk == 16 || dk == 32);
+  // (E = 64 cannot fit: its staged parameters alone, 49 984 floats, are 195 KiB)
+  return (E == 16 || E == 32) && (dk == 4 || dk == 8 || dk == 16 || dk == 32);
 }
 
 void check(const EncArgs& a) {
   if (a.T < 1 || a.T > 64 || !shape_ok(a.E, a.H) || a.FF != 4 * a.E ||
       bwd_smem(a) > 160 * 1024 || fwd_smem(a) > 160 * 1024)
     throw std::runtime_error(
-        "encoder_layer: unsupported shape (E in {16,32,64}, d_k in {4..32}, FF = 4E, T <= 64)");
+        "encoder_layer: unsupported shape (E in {16,32}, d_k in {4..32}, FF = 4E, T <= 64 and "
+        "within the 160 KiB LDS budget)");
 }
 
 template <bool BWD>
@@ -630,7 +632,6 @@ void launch(const EncArgs& a, size_t sm, hipStream_t s) {
   }
   TDFO_ENC(16, 4) TDFO_ENC(16, 8) TDFO_ENC(16, 16)
   TDFO_ENC(32, 4) TDFO_ENC(32, 8) TDFO_ENC(32, 16) TDFO_ENC(32, 32)
-  TDFO_ENC(64, 4) TDFO_ENC(64, 8) TDFO_ENC(64, 16) TDFO_ENC(64, 32)
 #undef TDFO_ENC
   throw std::runtime_error("encoder_layer: no kernel for this shape");
 }

@@ -1,5 +1,7 @@
 """float64 oracle of Linear(E -> V) + label-smoothed cross-entropy and the
-shared cases of the wide-hidden (E = 128 / 256) kernel tests.
+shared cases of its kernel tests: the wide-hidden kernels (WIDTHS, E = 128 /
+256) and the narrow ones (NARROW_WIDTHS, E = 16 / 32 / 64) run the same CASES,
+built per width by ``make_case`` / ``oracle_case``.
 
 The oracle materialises the [N, V] logits in fp64, so shapes stay small. It
 is written out by hand (no autograd) to be independent of
@@ -21,7 +23,8 @@ NAMES = ("dH", "loss", "dW", "db")
 # (V, N, hs): hs scales H (large logits exercise the running-max rescale)
 CASES = [(50, 7, 1.0), (130, 65, 1.0), (1000, 320, 1.0), (4099, 1030, 1.0), (5003, 200, 4.0),
          (5003, 200, 12.0), (70001, 320, 1.0)]
-WIDTHS = (128, 256)
+WIDTHS = (128, 256)             # linear_xent_mfma.hip
+NARROW_WIDTHS = (16, 32, 64)    # linear_xent.hip (16), linear_xent_wide.hip (32 / 64)
 # further shapes of the split test
 SPLIT_CASES = [(4099, 320), (130, 65)]
 
