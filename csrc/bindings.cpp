@@ -1560,8 +1560,16 @@ void colsum(const Tensor& x, const Tensor& out, bool accumulate) {
 }
 
 void auc_hist(const Tensor& logits, const Tensor& labels, int64_t nb, const Tensor& hist) {
-  TORCH_CHECK(hist.scalar_type() == at::kLong && hist.numel() == 2 * nb, "hist int64 [2*nb]");
-  TORCH_CHECK(logits.numel() == labels.numel(), "auc sizes");
+  // (first, and independent of the tensors: the limit of the kernel's LDS)
+  TORCH_CHECK(nb >= 1 && nb <= tdfo::AUC_HIST_MAX_NB, "auc_hist: nb = ", nb, " buckets need ",
+              2 * nb * 4, " bytes of LDS per block; supported: 1 <= nb <= ",
+              tdfo::AUC_HIST_MAX_NB, " (64 KiB)");
+  check_f32c(logits, "logits"); check_f32c(labels, "labels"); check_dev(hist, "hist");
+  TORCH_CHECK(hist.scalar_type() == at::kLong && hist.is_contiguous() && hist.numel() == 2 * nb,
+              "hist int64 contiguous [2*nb]");
+  TORCH_CHECK(logits.numel() == labels.numel() && logits.numel() < (1ll << 31), "auc sizes");
+  TORCH_CHECK(hist.device() == logits.device() && labels.device() == logits.device(),
+              "auc_hist: one device");
   tdfo::auc_hist(logits.data_ptr<float>(), labels.data_ptr<float>(), (int)logits.numel(), (int)nb,
                  reinterpret_cast<unsigned long long*>(hist.data_ptr<int64_t>()), cur_stream());
 }
@@ -2084,4 +2092,10 @@ TORCH_LIBRARY_IMPL(tdfo, CUDA, m) {
   m.impl("jagged_to_dense", jagged_to_dense);
   m.impl("dense_to_jagged", dense_to_jagged);
   m.impl("jagged_ids_to_dense", jagged_ids_to_dense);
+}
+
+// auc_hist's argument checks also answer CPU tensors (they end at "must be a
+// GPU tensor"; nothing is launched), so the nb limit can be tested without a GPU
+TORCH_LIBRARY_IMPL(tdfo, CPU, m) {
+  m.impl("auc_hist", auc_hist);
 }

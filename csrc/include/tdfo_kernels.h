@@ -449,6 +449,9 @@ void colsum_bf16(const uint16_t* x, int M, int N, int64_t ldx, float* part,
 int colsum_parts(int M);
 // AUC histogram: hist[2*nb]: [neg counts | pos counts] of sigmoid(logit)
 // bucketed uniformly on [0, 1] (tf.keras.metrics.AUC-style thresholds).
+// a block counts into 2 * nb LDS words: 64 KiB of dynamic LDS, the most a
+// launch may ask for, holds nb = 8192
+constexpr int AUC_HIST_MAX_NB = 8192;
 void auc_hist(const float* logits, const float* labels, int n, int nb,
               unsigned long long* hist, hipStream_t s);
 

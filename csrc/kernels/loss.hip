@@ -236,8 +236,10 @@ void head_bce(const uint16_t* H, int64_t ldh, int B, int K, const float* w,
     case 256: TDFO_HB(256); break;
     case 512: TDFO_HB(512); break;
     case 1024: TDFO_HB(1024); break;
+    default: throw std::runtime_error("head_bce: K must be 16, 32, ..., 1024");
   }
 #undef TDFO_HB
+  TDFO_CHECK_HIP(hipGetLastError());
 }
 
 void reduce_rows(const float* in, int rows, int64_t n, int64_t ld, float* out,
@@ -253,6 +255,7 @@ void reduce_rows(const float* in, int rows, int64_t n, int64_t ld, float* out,
     hipLaunchKernelGGL(reduce_rows_kernel<16>, dim3(blocks), dim3(256), 0, s, in,
                        rows, n, ld, out, accumulate, scale, idx);
   }
+  TDFO_CHECK_HIP(hipGetLastError());
 }
 
 // Split-K weight-grad slabs of several layers summed in ONE launch (the
@@ -347,17 +350,21 @@ void colsum_bf16(const uint16_t* x, int M, int N, int64_t ldx, float* part,
   if (M <= 0 || N <= 0) return;
   dim3 grid((N + 63) / 64, COLSUM_CHUNKS);
   hipLaunchKernelGGL(colsum_kernel, grid, dim3(256), 0, s, x, M, N, ldx, part);
+  TDFO_CHECK_HIP(hipGetLastError());
   reduce_rows(part, nparts, N, N, out, accumulate, 1.f, s);
 }
 
 void auc_hist(const float* logits, const float* labels, int n, int nb,
               unsigned long long* hist, hipStream_t s) {
   if (n <= 0) return;
+  // 2 * nb LDS counters: past AUC_HIST_MAX_NB the launch would be refused
+  if (nb < 1 || nb > AUC_HIST_MAX_NB) throw std::runtime_error("auc_hist: nb out of range");
   int blocks = (n + 255) / 256;
   if (blocks > 1024) blocks = 1024;
   hipLaunchKernelGGL(auc_hist_kernel, dim3(blocks), dim3(256),
                      (size_t)2 * nb * sizeof(unsigned int), s, logits, labels,
                      n, nb, hist);
+  TDFO_CHECK_HIP(hipGetLastError());
 }
 
 }  // namespace tdfo

@@ -124,17 +124,20 @@ int blocks_for(int64_t n, int per_thread) {
 void dense_optimizer(const DenseOptArgs& a, hipStream_t s) {
   if (a.n <= 0) return;
   hipLaunchKernelGGL(dense_opt_kernel, dim3(blocks_for(a.n, 4)), dim3(256), 0, s, a);
+  TDFO_CHECK_HIP(hipGetLastError());
 }
 
 void check_finite(const float* g, int64_t n, float* found_inf, hipStream_t s) {
   if (n <= 0) return;
   hipLaunchKernelGGL(finite_kernel, dim3(blocks_for(n, 4)), dim3(256), 0, s, g,
                      n, found_inf);
+  TDFO_CHECK_HIP(hipGetLastError());
 }
 
 void cast_f32_bf16(const float* x, uint16_t* y, int64_t n, hipStream_t s) {
   if (n <= 0) return;
   hipLaunchKernelGGL(cast_kernel, dim3(blocks_for(n, 4)), dim3(256), 0, s, x, y, n);
+  TDFO_CHECK_HIP(hipGetLastError());
 }
 
 }  // namespace tdfo

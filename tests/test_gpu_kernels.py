@@ -8,6 +8,7 @@ import torch
 
 from tdfo_amd import ops
 from tdfo_amd.ops import reference as ref
+from tests.tail_oracle import fixed_order_column_sums as _fixed_order_column_sums
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -963,26 +964,6 @@ def test_head_reduce_and_step_bumps():
     assert torch.allclose(grad.double(), p[:, : K + 1].sum(0), atol=1e-4)
     assert abs(float(loss) - (1.5 + float(p[:, K + 1].sum()))) < 1e-3
     assert float(h1[1]) == 5.0 and float(h2[1]) == 10.0 and float(h1[0]) == pytest.approx(0.1)
-
-
-def _fixed_order_column_sums(p, PH=16):
-    """head_reduce's summation order in fp32: per column, row phase ph sums
-    rows ph, ph + PH, ... into four accumulators (groups of four rows, a
-    partial last group into the first), then the phases are added in order."""
-    n = p.shape[0]
-    out = torch.zeros(p.shape[1], dtype=torch.float32)
-    for ph in range(PH):
-        s = [torch.zeros(p.shape[1], dtype=torch.float32) for _ in range(4)]
-        r = ph
-        while r + 3 * PH < n:
-            for q in range(4):
-                s[q] = s[q] + p[r + q * PH]
-            r += 4 * PH
-        while r < n:
-            s[0] = s[0] + p[r]
-            r += PH
-        out = out + ((s[0] + s[1]) + (s[2] + s[3]))
-    return out
 
 
 @pytest.mark.parametrize("nparts", [37, 512, 600])
