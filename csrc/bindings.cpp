@@ -1788,6 +1788,81 @@ void linear_xent(const Tensor& H, const Tensor& W, const Tensor& bias, const Ten
   tdfo::linear_xent(a, cur_stream());
 }
 
+void linear_xent_rows(const Tensor& H, const Tensor& W, const Tensor& bias, const Tensor& cand,
+                      const Tensor& target, double eps, const Tensor& dH, const Tensor& lossv,
+                      const c10::optional<Tensor>& dW, const c10::optional<Tensor>& db,
+                      const c10::optional<Tensor>& loss, const c10::optional<Tensor>& loss_acc,
+                      const c10::optional<Tensor>& corr) {
+  check_dev(H, "H"); check_dev(W, "W"); check_dev(bias, "bias"); check_dev(cand, "cand");
+  check_dev(target, "target"); check_dev(dH, "dH"); check_dev(lossv, "lossv");
+  TORCH_CHECK(H.scalar_type() == at::kFloat && H.dim() == 2 &&
+              (H.size(1) == 16 || H.size(1) == 32 || H.size(1) == 64 || H.size(1) == 128 ||
+               H.size(1) == 256) &&
+              H.is_contiguous() && aligned16(H.data_ptr()),
+              "linear_xent_rows: H fp32 [N,16|32|64|128|256]");
+  const int64_t N = H.size(0), E = H.size(1), M = cand.numel();
+  TORCH_CHECK(W.scalar_type() == at::kFloat && W.dim() == 2 && W.size(1) == E &&
+              W.is_contiguous() && aligned16(W.data_ptr()), "linear_xent_rows: W fp32 [V,E]");
+  const int64_t V = W.size(0);
+  TORCH_CHECK(bias.scalar_type() == at::kFloat && bias.numel() == V && bias.is_contiguous(),
+              "linear_xent_rows: bias fp32 [V]");
+  TORCH_CHECK(cand.scalar_type() == at::kLong && cand.is_contiguous(),
+              "linear_xent_rows: cand int64 [M]");
+  TORCH_CHECK(target.scalar_type() == at::kLong && target.numel() == N && target.is_contiguous(),
+              "linear_xent_rows: target int64 [N]");
+  TORCH_CHECK(dH.scalar_type() == at::kFloat && dH.sizes() == H.sizes() && dH.is_contiguous() &&
+              aligned16(dH.data_ptr()), "linear_xent_rows: dH");
+  TORCH_CHECK(lossv.scalar_type() == at::kFloat && lossv.numel() == N && lossv.is_contiguous(),
+              "linear_xent_rows: lossv");
+  TORCH_CHECK(N < (1 << 30) && M < (1ll << 31) && V < (1ll << 31), "linear_xent_rows: sizes");
+  tdfo::LinearXentRowsArgs a{};
+  a.H = H.data_ptr<float>(); a.W = W.data_ptr<float>(); a.bias = bias.data_ptr<float>();
+  a.cand = cand.data_ptr<int64_t>(); a.target = target.data_ptr<int64_t>();
+  a.N = (int)N; a.M = (int)M; a.V = V; a.eps = (float)eps;
+  a.dH = dH.data_ptr<float>(); a.lossv = lossv.data_ptr<float>();
+  if (corr) {
+    check_dev(*corr, "corr");
+    TORCH_CHECK(corr->scalar_type() == at::kFloat && corr->numel() == M && corr->is_contiguous(),
+                "linear_xent_rows: corr fp32 [M]");
+    a.corr = corr->data_ptr<float>();
+  }
+  if (dW.has_value()) {
+    TORCH_CHECK(db.has_value(), "linear_xent_rows: dW/db");
+    check_dev(*dW, "dW"); check_dev(*db, "db");
+    TORCH_CHECK(dW->sizes() == W.sizes() && dW->is_contiguous() &&
+                dW->scalar_type() == at::kFloat && aligned16(dW->data_ptr()) &&
+                db->numel() == V && db->scalar_type() == at::kFloat && db->is_contiguous(),
+                "linear_xent_rows: dW/db");
+    a.dW = dW->data_ptr<float>(); a.db = db->data_ptr<float>();
+  }
+  if (loss) {
+    check_dev(*loss, "loss");
+    TORCH_CHECK(loss->scalar_type() == at::kFloat && loss->numel() >= 1,
+                "linear_xent_rows: loss fp32 [1]");
+    a.loss = loss->data_ptr<float>();
+  }
+  if (loss_acc) {
+    check_dev(*loss_acc, "loss_acc");
+    TORCH_CHECK(loss && loss_acc->scalar_type() == at::kDouble && loss_acc->numel() >= 1,
+                "linear_xent_rows: loss_acc fp64 [1] (with loss)");
+    a.loss_acc = loss_acc->data_ptr<double>();
+  }
+  if (N == 0 || M == 0) return;
+  Tensor ws = at::empty({(int64_t)tdfo::linear_xent_rows_workspace((int)N, (int)M, (int)E)},
+                        H.options().dtype(at::kByte));
+  a.workspace = ws.data_ptr();
+  tdfo::linear_xent_rows(a, (int)E, cur_stream());
+}
+
+void sample_ids(int64_t seed, const Tensor& step, int64_t lo, int64_t hi, const Tensor& out) {
+  check_dev(step, "step"); check_dev(out, "out");
+  TORCH_CHECK(step.scalar_type() == at::kLong && step.numel() >= 1, "sample_ids: step int64 [1]");
+  TORCH_CHECK(out.scalar_type() == at::kLong && out.is_contiguous(), "sample_ids: out int64");
+  TORCH_CHECK(hi > lo && hi - lo < (1ll << 31), "sample_ids: need 0 < hi - lo < 2^31");
+  tdfo::sample_ids((uint32_t)(uint64_t)seed, step.data_ptr<int64_t>(), lo, hi, out.numel(),
+                   out.data_ptr<int64_t>(), cur_stream());
+}
+
 void check_offsets(const Tensor& off, int64_t B) {
   check_dev(off, "offsets");
   TORCH_CHECK(off.scalar_type() == at::kLong && off.is_contiguous() && off.numel() == B + 1,
@@ -2025,6 +2100,10 @@ TORCH_LIBRARY(tdfo, m) {
         "Tensor(a!) dH, Tensor(b!) lossv, Tensor(c!)? dW, Tensor(d!)? db, Tensor(e!)? loss, "
         "Tensor(f!)? loss_acc, Tensor(g!)[] ostate, Tensor? ohyper, float[] oparams, "
         "int okind) -> ()");
+  m.def("linear_xent_rows(Tensor H, Tensor W, Tensor bias, Tensor cand, Tensor target, float eps, "
+        "Tensor(a!) dH, Tensor(b!) lossv, Tensor(c!)? dW, Tensor(d!)? db, Tensor(e!)? loss, "
+        "Tensor(f!)? loss_acc, Tensor? corr) -> ()");
+  m.def("sample_ids(int seed, Tensor step, int lo, int hi, Tensor(a!) out) -> ()");
   m.def("jagged_to_dense(Tensor values, Tensor offsets, int T, float pad, Tensor(a!) out) -> ()");
   m.def("dense_to_jagged(Tensor dense, Tensor offsets, Tensor(a!) vgrad) -> ()");
   m.def("jagged_ids_to_dense(Tensor values, Tensor offsets, int pad, Tensor(a!) out) -> ()");
@@ -2089,6 +2168,8 @@ TORCH_LIBRARY_IMPL(tdfo, CUDA, m) {
   m.impl("two_tower", two_tower);
   m.impl("reduce_adam", reduce_adam);
   m.impl("linear_xent", linear_xent);
+  m.impl("linear_xent_rows", linear_xent_rows);
+  m.impl("sample_ids", sample_ids);
   m.impl("jagged_to_dense", jagged_to_dense);
   m.impl("dense_to_jagged", dense_to_jagged);
   m.impl("jagged_ids_to_dense", jagged_ids_to_dense);

@@ -501,6 +501,35 @@ int linear_xent_splits(int n);
 int linear_xent_impl(int impl);
 void linear_xent(const LinearXentArgs& a, hipStream_t s);
 
+// Linear + label-smoothed CE over a gathered candidate subset of W's rows
+// (linear_xent_rows.hip: sampled softmax), hidden widths 16 .. 256. cand[c] is
+// a row of W or a hole (outside [0, V): skipped, never read); target[n] is the
+// slot in cand of the token's positive (outside [0, M) or a hole: the token is
+// ignored). Non-hole candidates are distinct (the caller's promise). dW / db:
+// the rows named by valid candidates are assigned, every other row is left as
+// it was. linear_xent_splits also forces the candidate splits of its pass1.
+struct LinearXentRowsArgs {
+  const float* H;          // [N, E]
+  const float* W;          // [V, E]
+  const float* bias;       // [V]
+  const int64_t* cand;     // [M]
+  const int64_t* target;   // [N]
+  const float* corr;       // optional [M], added to the candidate's logit
+  int N; int M; int64_t V; float eps;
+  float* dH;               // [N, E] (scaled by 1/n_valid; zeros for ignored tokens)
+  float* lossv;            // [N] per-token loss (0 for ignored)
+  float* dW; float* db;    // optional [V, E], [V]
+  float* loss;             // optional scalar: sum(lossv) / max(1, n_valid)
+  double* loss_acc;        // optional running sum: += loss (device, fp64)
+  void* workspace;
+};
+size_t linear_xent_rows_workspace(int N, int M, int E);
+void linear_xent_rows(const LinearXentRowsArgs& a, int E, hipStream_t s);
+// out[i] = lo + ((hash3(seed, *step mod 2^32, i) * (hi - lo)) >> 32), i < n;
+// step is read on the device (a replayed graph draws fresh ids every step)
+void sample_ids(uint32_t seed, const int64_t* step, int64_t lo, int64_t hi, int64_t n,
+                int64_t* out, hipStream_t s);
+
 // -------------------------------------------------------- attention ----
 // Fused small-T MHA core (attention.hip): qkv [B,T,3E] fp32 (q|k|v, each
 // H x dk), key-padding mask from ids != pad_id, dropout(rate) from a counter

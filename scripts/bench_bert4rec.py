@@ -4,7 +4,9 @@
 --max-len / --embed-dim / --heads / --layers pick another shape, e.g. the
 published BERT4Rec one: --max-len 200 --embed-dim 64 (T > 64 runs the tiled
 attention and wide LayerNorm kernels; the fused block covers T <= 64).
---causal trains the next-item (causal attention) model on shifted labels."""
+--causal trains the next-item (causal attention) model on shifted labels.
+--negatives S trains with the sampled-softmax loss over S shared negatives
+(0: the full softmax)."""
 import argparse
 import json
 import sys
@@ -30,6 +32,8 @@ def main():
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--causal", action="store_true",
                     help="causal attention, per-position input block, labels = the next item")
+    ap.add_argument("--negatives", type=int, default=0,
+                    help="sampled softmax over this many shared negatives (0: full softmax)")
     ap.add_argument("--torch-encoder", action="store_true",
                     help="torch reference attention/LayerNorm instead of the HIP kernels")
     a = ap.parse_args()
@@ -39,6 +43,8 @@ def main():
     dev = "cuda"
     T = a.max_len
     ckw = {"causal": True} if a.causal else {}
+    if a.negatives:
+        ckw.update(loss="sampled", num_negatives=a.negatives)
     tr = Bert4RecTrainer(a.items, T, a.embed_dim, a.heads, a.layers, a.batch, device=dev, **ckw)
     g = torch.Generator(device=dev).manual_seed(0)
     pool = []
@@ -68,6 +74,7 @@ def main():
     print(json.dumps({"model": "bert4rec", "batch": a.batch, "vocab": a.items + 2,
                       "max_len": T, "embed_dim": a.embed_dim, "heads": a.heads,
                       "layers": a.layers, "causal": a.causal,
+                      "negatives": a.negatives,
                       "graph": not a.no_graph, "fused_encoder": not a.torch_encoder, "ms_per_step": round(el / a.steps * 1e3, 4),
                       "sequences_per_sec": round(a.batch * a.steps / el, 1),
                       "loss": round(tr.pop_loss(), 4)}))

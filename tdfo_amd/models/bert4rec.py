@@ -30,6 +30,13 @@ j <= i, and a per-position input block dropout(LayerNorm_E(item_emb + pos))
 the future). Labels are the next item at every position; PAD labels are
 ignored by the same fused Linear+CE. Causal models take the per-op path at
 every shape (encoder.hip's fused block has no causal form).
+
+``Bert4RecTrainer(loss="sampled", num_negatives=S)`` trains either model with
+a sampled softmax: every position against its positive and S uniform negatives
+shared by the batch (``ops.sample_ids`` / ``ops.xent_candidates`` /
+``sampled_linear_cross_entropy`` on ``tdfo::linear_xent_rows``). The output
+layer's gradient is then dense in the flat buffer, zero outside the candidates,
+and the flat optimizer steps it; eval and checkpoints are the same.
 """
 from __future__ import annotations
 
@@ -475,6 +482,47 @@ def linear_cross_entropy(H, W, b, labels, eps=0.1, loss_acc=None, unit_grad=Fals
                                unit_grad, step)
 
 
+class _SampledXentFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, H, W, b, cand, target, eps, loss_acc, unit_grad):
+        N = H.shape[0]
+        dH = torch.empty_like(H)
+        lossv = torch.empty(N, dtype=torch.float32, device=H.device)
+        # as _LinearXentFn: with a unit gradient the kernel writes the
+        # candidates' rows straight into the (zeroed) .grad buffers
+        direct = bool(unit_grad and W.grad is not None and b.grad is not None and
+                      W.grad.is_contiguous() and b.grad.is_contiguous())
+        dW = W.grad if direct else torch.zeros_like(W)
+        db = b.grad if direct else torch.zeros_like(b)
+        loss = torch.empty(1, dtype=torch.float32, device=H.device)
+        ops.linear_xent_rows(H, W, b, cand, target, eps, dH, lossv, dW, db, loss=loss,
+                             loss_acc=loss_acc)
+        ctx.save_for_backward(dH, dW, db)
+        ctx.unit_grad = unit_grad
+        ctx.direct = direct
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        dH, dW, db = ctx.saved_tensors
+        if ctx.unit_grad:      # caller's promise: the loss is backward()'s root (g == 1)
+            if ctx.direct:
+                return dH, None, None, None, None, None, None, None
+            return dH, dW, db, None, None, None, None, None
+        return dH * g, dW * g, db * g, None, None, None, None, None
+
+
+def sampled_linear_cross_entropy(H, W, b, cand, target, eps=0.1, loss_acc=None, unit_grad=False):
+    """mean label-smoothed CE of every token against the candidate rows W[cand]
+    (sampled softmax; ops.linear_xent_rows: cand holds holes, target the slot
+    of the token's positive or -1), fused. loss_acc / unit_grad as in
+    linear_cross_entropy: with unit_grad and existing contiguous W.grad /
+    b.grad (zeroed by the caller) the kernel writes the candidates' rows
+    there; the gradient is exactly zero everywhere else."""
+    return _SampledXentFn.apply(H.contiguous(), W, b, cand.contiguous(), target.contiguous(), eps,
+                                loss_acc, unit_grad)
+
+
 class Bert4Rec(nn.Module):
     """Reference parameter names are preserved (state_dict() keys match
     torchrec's Bert4Rec except the item table, exported by the trainer)."""
@@ -560,8 +608,16 @@ class Bert4RecTrainer:
                  n_layers: int = 2, batch_size: int = 16, lr: float = 3e-4, wd: float = 1e-4,
                  device="cpu", mode: str = "local", group=None, rank: int = 0, world: int = 1,
                  dropout: float = 0.1, seed: int = 42, label_smoothing: float = 0.1,
-                 causal: bool = False):
+                 causal: bool = False, loss: str = "full", num_negatives: int = 0):
         self.V = n_items + 2                     # 0 = PAD, n_items + 1 = MASK
+        if loss not in ("full", "sampled"):
+            raise ValueError(f"loss must be 'full' or 'sampled', got {loss!r}")
+        if loss == "sampled" and not 1 <= num_negatives <= n_items:
+            raise ValueError(f"loss='sampled' needs 1 <= num_negatives <= n_items = {n_items}, "
+                             f"got {num_negatives}")
+        # "sampled": every position against its positive and num_negatives
+        # shared uniform negatives (sampled softmax) instead of the catalogue
+        self.loss_kind, self.S = loss, int(num_negatives) if loss == "sampled" else 0
         self.T, self.E, self.B = max_len, embed_dim, batch_size
         self.causal = bool(causal)               # next-item objective (module docstring)
         self.device = dev = torch.device(device)
@@ -598,7 +654,9 @@ class Bert4RecTrainer:
         # the flat optimizer steps the rest. More ranks all-reduce the
         # gradient first. TDFO_XENT_FUSED_STEP=0: the unfused path (A/B).
         self._xent_step = None
-        if (world == 1 and dev.type == "cuda" and not self.opt.dynamic_scale
+        # (sampled loss: the output layer's gradient is dense in the flat buffer,
+        # zero outside the candidates, and the flat optimizer steps it)
+        if (loss == "full" and world == 1 and dev.type == "cuda" and not self.opt.dynamic_scale
                 and os.environ.get("TDFO_XENT_FUSED_STEP", "1") != "0"):
             out = self.model.out
             mw, vw = self.opt.moments(out.weight)
@@ -618,6 +676,13 @@ class Bert4RecTrainer:
             self._attach_direct_grads()
         self.seqs = torch.zeros(batch_size, max_len, dtype=torch.int64, device=dev)
         self.labels = torch.zeros(batch_size, max_len, dtype=torch.int64, device=dev)
+        if self.S:
+            # the step's negatives, candidate list (labels + negatives, holes
+            # -1) and every token's slot in it: static buffers
+            self.neg = torch.zeros(self.S, dtype=torch.int64, device=dev)
+            self.cand = torch.full((ntok + self.S,), -1, dtype=torch.int64, device=dev)
+            self.cand_target = torch.full((ntok,), -1, dtype=torch.int64, device=dev)
+            self._neg_seed = (seed * 0x9E3779B1 + rank * 0x85EBCA77 + 0x5A3D9E1) & 0xFFFFFFFF
         self.loss_sum = torch.zeros(1, dtype=torch.float64, device=dev)
         self.steps = 0
         self.metric_sums = torch.zeros(len(METRIC_NAMES) + 1, dtype=torch.float64, device=dev)
@@ -699,9 +764,19 @@ class Bert4RecTrainer:
         self.item.train()
         x = self._embed(seqs)
         h = self.model.encode(x, seqs)
-        loss = linear_cross_entropy(h.reshape(-1, self.E), self.model.out.weight,
-                                    self.model.out.bias, labels.reshape(-1), self.eps,
-                                    loss_acc=self.loss_sum, unit_grad=True, step=self._xent_step)
+        if self.S:
+            # negatives uniform over the items 1 .. n_items (PAD / MASK never),
+            # keyed by (seed, rank, rng_step): fresh in every replayed step
+            ops.sample_ids(self._neg_seed, self.model.rng_step, 1, self.V - 1, self.neg)
+            ops.xent_candidates(labels.reshape(-1), self.neg, PAD_ID, self.cand, self.cand_target)
+            loss = sampled_linear_cross_entropy(h.reshape(-1, self.E), self.model.out.weight,
+                                                self.model.out.bias, self.cand, self.cand_target,
+                                                self.eps, loss_acc=self.loss_sum, unit_grad=True)
+        else:
+            loss = linear_cross_entropy(h.reshape(-1, self.E), self.model.out.weight,
+                                        self.model.out.bias, labels.reshape(-1), self.eps,
+                                        loss_acc=self.loss_sum, unit_grad=True,
+                                        step=self._xent_step)
         # the root gradient from a persistent 1 (implicit backward() fills a
         # fresh ones tensor every step: one fill launch)
         one = getattr(self, "_one", None)

@@ -910,8 +910,69 @@ def linear_xent_splits(n: int = -1) -> int:
     (csrc/kernels/linear_xent_mfma.hip): 0 auto (default), n > 0 forces n
     (clamped to V); n < 0 only reads it. Returns the previous value. Results
     differ between split counts only by fp32 association; for a fixed count
-    they are bit-reproducible. Other widths do not look at it."""
+    they are bit-reproducible. The full-softmax kernels of the other widths do
+    not look at it; linear_xent_rows takes it as its number of candidate
+    splits at every width."""
     return int(_native().linear_xent_splits(int(n)))
+
+
+def linear_xent_rows(H, W, bias, cand, target, eps, dH, lossv, dW=None, db=None, loss=None,
+                     loss_acc=None, corr=None):
+    """Linear + label-smoothed CE of every token against a gathered subset of
+    W's rows (sampled softmax), fwd+bwd, no [N, M] logits
+    (csrc/kernels/linear_xent_rows.hip; E in 16 / 32 / 64 / 128 / 256 on the GPU).
+    cand int64 [M]: rows of W; an entry outside [0, V) is a hole (skipped,
+    never read); the other entries must be distinct. target int64 [N]: the
+    slot in cand of the token's positive; outside [0, M), or naming a hole,
+    ignores the token. corr fp32 [M] (optional) is added to the candidate's
+    logit (a logQ correction; no gradient). dH / lossv are written for every
+    token (zeros for ignored ones); dW / db only in the rows named by valid
+    candidates (assigned; every other row keeps what it held). loss / loss_acc
+    as in linear_xent. N == 0 or M == 0: nothing is written."""
+    if _gpu(H):
+        _native().linear_xent_rows(H, W, bias, cand, target, float(eps), dH, lossv, dW, db, loss,
+                                   loss_acc, corr)
+    elif H.shape[0] and cand.numel():
+        nv = ref.linear_xent_rows(H, W, bias, cand, target, eps, dH, lossv, dW, db, corr)
+        if loss is not None:
+            loss.view(-1)[0] = lossv.sum() / max(1, nv)
+            if loss_acc is not None:
+                loss_acc.view(-1)[0] += loss.view(-1)[0].double()
+
+
+def sample_ids(seed, step, lo, hi, out):
+    """out[i] = lo + ((hash3(seed, step mod 2^32, i) * (hi - lo)) >> 32): ids
+    uniform in [lo, hi) from the counter hash of tdfo_common.h. step: int64
+    tensor [1] read on the device (a replayed graph draws fresh ids each
+    step); 0 < hi - lo < 2^31. GPU kernel and CPU mirror agree bit for bit."""
+    if not 0 < hi - lo < 2 ** 31:
+        raise ValueError("sample_ids: need 0 < hi - lo < 2^31")
+    if _gpu(out):
+        _native().sample_ids(int(seed) & 0xFFFFFFFF, step, int(lo), int(hi), out)
+    else:
+        ref.sample_ids(seed, step, lo, hi, out)
+
+
+_CAND_BITS = 31
+_CAND_SENT = (1 << _CAND_BITS) - 1      # above every row id (V < 2^31 - 1): sorts last
+
+
+def xent_candidates(labels, neg, ignore, cand, target):
+    """Candidate list of one sampled-softmax step for ``linear_xent_rows``:
+    cand [N + S] = the sorted union of the non-ignored labels [N] and the
+    negatives [S], every repeated entry and every ignored label a hole (-1);
+    target [N] = the slot of the head of the run holding labels[n], -1 when
+    ignored. Static shapes, no host sync (graph-capturable)."""
+    labels, neg = labels.reshape(-1), neg.reshape(-1)
+    ign = labels == ignore
+    keys = torch.cat([labels.masked_fill(ign, _CAND_SENT), neg])
+    vals = torch.arange(keys.numel(), dtype=torch.int32, device=keys.device)
+    sk, _ = sort_pairs(keys, vals, _CAND_BITS)
+    hole = sk == _CAND_SENT
+    hole[1:] |= sk[1:] == sk[:-1]
+    cand.copy_(sk.masked_fill(hole, -1))
+    pos = torch.searchsorted(sk, labels)                   # left: the head of the run
+    target.copy_(pos.masked_fill(ign, -1))
 
 
 def jagged_to_dense(values, offsets, T, pad, out):

@@ -631,6 +631,55 @@ def linear_xent(H, W, bias, labels, eps, ignore, dH, lossv, dW=None, db=None):
         db.copy_(br.grad)
 
 
+def linear_xent_rows(H, W, bias, cand, target, eps, dH, lossv, dW=None, db=None, corr=None):
+    """Oracle of the candidate-subset Linear+CE (sampled softmax): logits of
+    every token against the valid rows W[cand] (+ bias, + corr), CrossEntropy
+    with label_smoothing over those candidates, mean over the non-ignored
+    tokens. A cand entry outside [0, V) is a hole; a target outside [0, M) or
+    naming a hole ignores the token. dW / db: only the rows named by valid
+    candidates are assigned (every other row keeps what it held).
+    Returns the number of valid tokens."""
+    V, M = W.shape[0], cand.numel()
+    cvalid = (cand >= 0) & (cand < V)
+    slots = torch.nonzero(cvalid).view(-1)                 # ascending: the compacted order
+    rows = cand[slots]
+    pos = torch.full((M + 1,), -100, dtype=torch.int64)    # slot -> compacted position
+    pos[slots] = torch.arange(slots.numel())
+    inr = (target >= 0) & (target < M)
+    y = pos[torch.where(inr, target, torch.full_like(target, M))]
+    nv = int((y >= 0).sum())
+    lossv.zero_()
+    dH.zero_()
+    if nv == 0:                         # (nothing valid: dW / db are not written)
+        return nv
+    with torch.enable_grad():
+        Hr = H.detach().float().clone().requires_grad_(True)
+        Wc = W.detach().float()[rows].clone().requires_grad_(True)
+        bc = bias.detach().float()[rows].clone().requires_grad_(True)
+        logits = Hr @ Wc.t() + bc
+        if corr is not None:
+            logits = logits + corr.detach().float()[slots]
+        per = torch.nn.functional.cross_entropy(logits, y, ignore_index=-100,
+                                                label_smoothing=eps, reduction="none")
+        (per.sum() / max(1, nv)).backward()
+    lossv.copy_(per.detach())
+    dH.copy_(Hr.grad)
+    if dW is not None:
+        dW[rows] = Wc.grad
+        db[rows] = bc.grad
+    return nv
+
+
+def sample_ids(seed, step, lo, hi, out):
+    """Python mirror of the GPU sampler: out[i] = lo + ((hash3(seed, step mod
+    2^32, i) * (hi - lo)) >> 32), the counter hash of tdfo_common.h."""
+    n = out.numel()
+    a = torch.full((n,), int(seed) & _M32, dtype=torch.int64)
+    b = (step.detach().cpu().view(-1)[0] & _M32).expand(n)
+    h = _hash3(a, b, torch.arange(n, dtype=torch.int64))
+    out.copy_((lo + ((h * (hi - lo)) >> 32)).view_as(out))
+
+
 def _bag_positions(offsets, T):
     lens = (offsets[1:] - offsets[:-1])
     B = lens.numel()

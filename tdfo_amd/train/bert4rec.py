@@ -65,7 +65,9 @@ def run(cfg: Config, out_dir: str = ".", device: Optional[str] = None) -> List[D
     B, EB = cfg.per_device_train_batch_size, cfg.per_device_eval_batch_size
     tr = Bert4RecTrainer(n_items, cfg.max_len, cfg.embed_dim, cfg.n_heads, cfg.n_layers, B,
                          cfg.learning_rate, cfg.weight_decay, dev, mode, group, rank, world,
-                         seed=cfg.seed, causal=causal)
+                         seed=cfg.seed, causal=causal,
+                         loss="sampled" if cfg.train_loss == "sampled_softmax" else "full",
+                         num_negatives=cfg.num_negatives)
     data_dev = dev if cfg.data_on_device else torch.device("cpu")
     train = DeviceColumns({"seqs": train_cols["train_interactions"].astype("int64"),
                            "labels": train_cols["labels"].astype("int64")}, data_dev)

@@ -1,0 +1,167 @@
+"""Sampled-softmax training on the CPU: the reference op against the fp64
+oracle, the sampler's mirror, the candidate builder, the config keys and the
+Bert4RecTrainer(loss="sampled") step."""
+import pytest
+import torch
+import torch.nn.functional as F
+
+from tdfo_amd import config as cfgmod
+from tdfo_amd import ops
+from tdfo_amd.models.bert4rec import Bert4RecTrainer
+from tests import xent_rows_oracle as xr
+from tests.test_sasrec import _next_item_batch
+
+
+@pytest.mark.parametrize("N,M,wc", [(65, 64, False), (320, 129, True)])
+def test_reference_matches_fp64_oracle(N, M, wc):
+    E, FILL = 16, 1.0
+    H, W, b, cand, target, corr = xr.make_case(N, M, E, xr.V, 1.0, wc)
+    want = xr.oracle_case(N, M, E, xr.V, 1.0, wc)
+    dH, lv = torch.ones(N, E), torch.ones(N)
+    dW, db = torch.full((xr.V, E), FILL), torch.full((xr.V,), FILL)
+    loss, acc = torch.zeros(1), torch.full((1,), 2.0, dtype=torch.float64)
+    ops.linear_xent_rows(H, W, b, cand, target, xr.EPS, dH, lv, dW, db, loss=loss, loss_acc=acc,
+                         corr=corr)
+    named = torch.zeros(xr.V, dtype=torch.bool)
+    named[cand[xr.valid_slots(cand, xr.V)]] = True
+    assert bool((dW[~named] == FILL).all()) and bool((db[~named] == FILL).all())
+    got = [dH, lv, dW[named], db[named], loss[0]]
+    ref = [want[0], want[1], want[2][named], want[3][named], want[4]]
+    for k, a, r in zip(xr.NAMES, got, ref):
+        assert xr.rel_err(a, r) < 1e-5, k
+    assert abs(float(acc) - 2.0 - float(loss)) < 1e-6
+
+
+def test_sampler_uniform_and_fresh():
+    """200 000 draws over 1000 ids: every bin within 6 standard deviations of
+    its mean (binomial), ids in [lo, hi), another vector at the next step."""
+    n, lo, hi = 200_000, 5, 1005
+    p = 1.0 / (hi - lo)
+    sd = (n * p * (1 - p)) ** 0.5
+    worst = 0.0
+    for seed, step in ((42, 0), (42, 1), (7, 123456), (0, 2 ** 32 + 3)):
+        out = torch.empty(n, dtype=torch.int64)
+        ops.sample_ids(seed, torch.tensor([step]), lo, hi, out)
+        assert int(out.min()) >= lo and int(out.max()) < hi
+        dev = (torch.bincount(out - lo, minlength=hi - lo).double() - n * p).abs().max() / sd
+        worst = max(worst, float(dev))
+        nxt = torch.empty(n, dtype=torch.int64)
+        ops.sample_ids(seed, torch.tensor([step + 1]), lo, hi, nxt)
+        assert not torch.equal(out, nxt)
+    print(f"worst bin: {worst:.2f} standard deviations")
+    assert worst < 6.0
+    a, b = torch.empty(64, dtype=torch.int64), torch.empty(64, dtype=torch.int64)
+    ops.sample_ids(42, torch.tensor([3]), lo, hi, a)
+    ops.sample_ids(42, torch.tensor([2 ** 32 + 3]), lo, hi, b)       # step mod 2^32
+    assert torch.equal(a, b)
+    with pytest.raises(ValueError, match="hi - lo"):
+        ops.sample_ids(1, torch.tensor([0]), 5, 5, a)
+
+
+def test_candidate_builder():
+    labels, neg = xr.candidate_case()
+    cand = torch.zeros(labels.numel() + neg.numel(), dtype=torch.int64)
+    target = torch.zeros(labels.numel(), dtype=torch.int64)
+    ops.xent_candidates(labels, neg, 0, cand, target)
+    xr.check_candidates(labels, neg, cand, target)
+    # every label ignored: only the negatives remain
+    ops.xent_candidates(torch.zeros_like(labels), neg, 0, cand, target)
+    xr.check_candidates(torch.zeros_like(labels), neg, cand, target)
+
+
+def test_config_keys():
+    f = cfgmod.Config.__dataclass_fields__
+    assert f["train_loss"].default == "full" and f["num_negatives"].default == 0
+    cfg = cfgmod.from_dict({"model": "bert4rec", "train_loss": "sampled_softmax",
+                            "num_negatives": 64})
+    assert cfg.train_loss == "sampled_softmax" and cfg.num_negatives == 64
+    assert cfgmod.from_dict({"model": "bert4rec"}).train_loss == "full"
+    with pytest.raises(ValueError, match="full\\|sampled_softmax"):
+        cfgmod.from_dict({"model": "bert4rec", "train_loss": "sampled"})
+    with pytest.raises(ValueError, match="num_negatives"):
+        cfgmod.from_dict({"model": "bert4rec", "train_loss": "sampled_softmax"})
+    with pytest.raises(ValueError, match="bert4rec"):
+        cfgmod.from_dict({"model": "dlrm", "train_loss": "sampled_softmax", "num_negatives": 8})
+    with pytest.raises(ValueError, match="num_negatives"):
+        Bert4RecTrainer(30, 8, 16, 2, 1, 2, loss="sampled", num_negatives=0)
+    with pytest.raises(ValueError, match="num_negatives"):
+        Bert4RecTrainer(30, 8, 16, 2, 1, 2, loss="sampled", num_negatives=31)
+    with pytest.raises(ValueError, match="loss"):
+        Bert4RecTrainer(30, 8, 16, 2, 1, 2, loss="bce")
+
+
+N_ITEMS, T, E, B, S = 300, 20, 16, 16, 32
+
+
+def _trainer(**kw):
+    return Bert4RecTrainer(N_ITEMS, T, E, 2, 2, B, lr=3e-3, device="cpu", dropout=0.0, seed=3,
+                           causal=True, **kw)
+
+
+def test_sampled_step_equals_plain_autograd():
+    """One step equals autograd through F.cross_entropy on the gathered logits
+    of the same candidates followed by the same flat optimizer; rows of
+    out.weight outside the candidates move only by the zero-gradient step."""
+    a, b = _trainer(loss="sampled", num_negatives=S), _trainer(loss="sampled", num_negatives=S)
+    assert torch.equal(a.opt.flat, b.opt.flat)
+    s, l = _next_item_batch(torch.Generator().manual_seed(1), B, T, N_ITEMS)
+    W0 = a.model.out.weight.detach().clone()
+    a.load_batch(s, l)
+    a.step()
+    assert a.cand.numel() == B * T + S
+    cand, target = a.cand.clone(), a.cand_target.clone()
+    xr.check_candidates(l.reshape(-1), a.neg, cand, target)
+    assert int(a.neg.min()) >= 1 and int(a.neg.max()) <= N_ITEMS
+    # b: the same step by hand
+    ops.bump(b._counters)
+    b.opt.zero_grads()
+    b.model.train()
+    b.item.train()
+    h = b.model.encode(b._embed(s), s).reshape(-1, E)
+    slots = torch.nonzero(cand >= 0).view(-1)
+    pos = torch.full((cand.numel(),), -100, dtype=torch.int64)
+    pos[slots] = torch.arange(slots.numel())
+    y = torch.where(target >= 0, pos[target.clamp_min(0)], torch.full_like(target, -100))
+    rows = cand[slots]
+    logits = h @ b.model.out.weight[rows].t() + b.model.out.bias[rows]
+    loss = F.cross_entropy(logits, y, ignore_index=-100, label_smoothing=b.eps)
+    loss.backward()
+    b.opt.step()
+    assert abs(a.pop_loss() - float(loss.detach())) < 1e-5
+    torch.testing.assert_close(a.opt.flat, b.opt.flat, rtol=1e-5, atol=1e-5)
+    torch.testing.assert_close(a.item.weight, b.item.weight, rtol=1e-5, atol=1e-5)
+    # rows outside the candidates: the step of a zero gradient (Adam's L2 decay
+    # term alone), i.e. what a trainer does whose gradient is zero everywhere
+    z = _trainer(loss="sampled", num_negatives=S)
+    ops.bump(z._counters)
+    z.opt.zero_grads()
+    z.opt.step()
+    out = torch.ones(a.V, dtype=torch.bool)
+    out[rows] = False
+    assert int(out.sum()) > 0
+    assert torch.equal(a.model.out.weight.detach()[out], z.model.out.weight.detach()[out])
+    assert not torch.equal(a.model.out.weight.detach()[~out], W0[~out])
+
+
+def test_sampled_trainer_learns():
+    tr = _trainer(loss="sampled", num_negatives=S)
+    s, l = _next_item_batch(torch.Generator().manual_seed(0), B, T, N_ITEMS)
+    losses = []
+    for i in range(30):
+        tr.load_batch(s, l)
+        tr.step()
+        if i % 10 == 9:
+            losses.append(tr.pop_loss())
+    assert losses[-1] < losses[0], losses
+
+
+def test_full_loss_is_todays_trainer():
+    a, b = _trainer(), _trainer(loss="full", num_negatives=0)
+    g = torch.Generator().manual_seed(2)
+    for _ in range(2):
+        s, l = _next_item_batch(g, B, T, N_ITEMS)
+        for t in (a, b):
+            t.load_batch(s, l)
+            t.step()
+    assert torch.equal(a.opt.flat, b.opt.flat) and torch.equal(a.item.weight, b.item.weight)
+    assert not hasattr(b, "cand")
