@@ -1854,6 +1854,70 @@ void linear_xent_rows(const Tensor& H, const Tensor& W, const Tensor& bias, cons
   tdfo::linear_xent_rows(a, (int)E, cur_stream());
 }
 
+void linear_bce_rows(const Tensor& H, const Tensor& W, const Tensor& bias, const Tensor& labels,
+                     const Tensor& order, const Tensor& negs, double beta, int64_t ignore,
+                     const Tensor& dH, const Tensor& lossv, const c10::optional<Tensor>& dW,
+                     const c10::optional<Tensor>& db, const c10::optional<Tensor>& loss,
+                     const c10::optional<Tensor>& loss_acc) {
+  check_dev(H, "H"); check_dev(W, "W"); check_dev(bias, "bias"); check_dev(labels, "labels");
+  check_dev(order, "order"); check_dev(negs, "negs"); check_dev(dH, "dH");
+  check_dev(lossv, "lossv");
+  TORCH_CHECK(H.scalar_type() == at::kFloat && H.dim() == 2 &&
+              (H.size(1) == 16 || H.size(1) == 32 || H.size(1) == 64 || H.size(1) == 128 ||
+               H.size(1) == 256) &&
+              H.is_contiguous() && aligned16(H.data_ptr()),
+              "linear_bce_rows: H fp32 [N,16|32|64|128|256]");
+  const int64_t N = H.size(0), E = H.size(1), S = negs.numel();
+  TORCH_CHECK(W.scalar_type() == at::kFloat && W.dim() == 2 && W.size(1) == E &&
+              W.is_contiguous() && aligned16(W.data_ptr()), "linear_bce_rows: W fp32 [V,E]");
+  const int64_t V = W.size(0);
+  TORCH_CHECK(bias.scalar_type() == at::kFloat && bias.numel() == V && bias.is_contiguous(),
+              "linear_bce_rows: bias fp32 [V]");
+  TORCH_CHECK(labels.scalar_type() == at::kLong && labels.numel() == N && labels.is_contiguous(),
+              "linear_bce_rows: labels int64 [N]");
+  TORCH_CHECK(order.scalar_type() == at::kInt && order.numel() == N && order.is_contiguous(),
+              "linear_bce_rows: order int32 [N]");
+  TORCH_CHECK(negs.scalar_type() == at::kLong && negs.is_contiguous(),
+              "linear_bce_rows: negs int64 [S]");
+  TORCH_CHECK(dH.scalar_type() == at::kFloat && dH.sizes() == H.sizes() && dH.is_contiguous() &&
+              aligned16(dH.data_ptr()), "linear_bce_rows: dH");
+  TORCH_CHECK(lossv.scalar_type() == at::kFloat && lossv.numel() == N && lossv.is_contiguous(),
+              "linear_bce_rows: lossv");
+  TORCH_CHECK(N < (1 << 30) && S < (1ll << 31) && V < (1ll << 31), "linear_bce_rows: sizes");
+  tdfo::LinearBceRowsArgs a{};
+  a.H = H.data_ptr<float>(); a.W = W.data_ptr<float>(); a.bias = bias.data_ptr<float>();
+  a.labels = labels.data_ptr<int64_t>(); a.order = order.data_ptr<int32_t>();
+  a.negs = negs.data_ptr<int64_t>();
+  a.N = (int)N; a.S = (int)S; a.V = V; a.ignore = ignore; a.beta = (float)beta;
+  a.dH = dH.data_ptr<float>(); a.lossv = lossv.data_ptr<float>();
+  if (dW.has_value()) {
+    TORCH_CHECK(db.has_value(), "linear_bce_rows: dW/db");
+    check_dev(*dW, "dW"); check_dev(*db, "db");
+    TORCH_CHECK(dW->sizes() == W.sizes() && dW->is_contiguous() &&
+                dW->scalar_type() == at::kFloat && aligned16(dW->data_ptr()) &&
+                db->numel() == V && db->scalar_type() == at::kFloat && db->is_contiguous(),
+                "linear_bce_rows: dW/db");
+    a.dW = dW->data_ptr<float>(); a.db = db->data_ptr<float>();
+  }
+  if (loss) {
+    check_dev(*loss, "loss");
+    TORCH_CHECK(loss->scalar_type() == at::kFloat && loss->numel() >= 1,
+                "linear_bce_rows: loss fp32 [1]");
+    a.loss = loss->data_ptr<float>();
+  }
+  if (loss_acc) {
+    check_dev(*loss_acc, "loss_acc");
+    TORCH_CHECK(loss && loss_acc->scalar_type() == at::kDouble && loss_acc->numel() >= 1,
+                "linear_bce_rows: loss_acc fp64 [1] (with loss)");
+    a.loss_acc = loss_acc->data_ptr<double>();
+  }
+  if (N == 0 || S == 0) return;
+  Tensor ws = at::empty({(int64_t)tdfo::linear_bce_rows_workspace((int)N, (int)S, (int)E)},
+                        H.options().dtype(at::kByte));
+  a.workspace = ws.data_ptr();
+  tdfo::linear_bce_rows(a, (int)E, cur_stream());
+}
+
 void sample_ids(int64_t seed, const Tensor& step, int64_t lo, int64_t hi, const Tensor& out) {
   check_dev(step, "step"); check_dev(out, "out");
   TORCH_CHECK(step.scalar_type() == at::kLong && step.numel() >= 1, "sample_ids: step int64 [1]");
@@ -2103,6 +2167,9 @@ TORCH_LIBRARY(tdfo, m) {
   m.def("linear_xent_rows(Tensor H, Tensor W, Tensor bias, Tensor cand, Tensor target, float eps, "
         "Tensor(a!) dH, Tensor(b!) lossv, Tensor(c!)? dW, Tensor(d!)? db, Tensor(e!)? loss, "
         "Tensor(f!)? loss_acc, Tensor? corr) -> ()");
+  m.def("linear_bce_rows(Tensor H, Tensor W, Tensor bias, Tensor labels, Tensor order, Tensor negs, "
+        "float beta, int ignore, Tensor(a!) dH, Tensor(b!) lossv, Tensor(c!)? dW, Tensor(d!)? db, "
+        "Tensor(e!)? loss, Tensor(f!)? loss_acc) -> ()");
   m.def("sample_ids(int seed, Tensor step, int lo, int hi, Tensor(a!) out) -> ()");
   m.def("jagged_to_dense(Tensor values, Tensor offsets, int T, float pad, Tensor(a!) out) -> ()");
   m.def("dense_to_jagged(Tensor dense, Tensor offsets, Tensor(a!) vgrad) -> ()");
@@ -2169,6 +2236,7 @@ TORCH_LIBRARY_IMPL(tdfo, CUDA, m) {
   m.impl("reduce_adam", reduce_adam);
   m.impl("linear_xent", linear_xent);
   m.impl("linear_xent_rows", linear_xent_rows);
+  m.impl("linear_bce_rows", linear_bce_rows);
   m.impl("sample_ids", sample_ids);
   m.impl("jagged_to_dense", jagged_to_dense);
   m.impl("dense_to_jagged", dense_to_jagged);

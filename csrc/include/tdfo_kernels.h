@@ -530,6 +530,35 @@ void linear_xent_rows(const LinearXentRowsArgs& a, int E, hipStream_t s);
 void sample_ids(uint32_t seed, const int64_t* step, int64_t lo, int64_t hi, int64_t n,
                 int64_t* out, hipStream_t s);
 
+// Linear + BCE / gBCE of every token against its positive row labels[n] and the
+// shared negative rows negs[c] of W (linear_bce_rows.hip), hidden widths
+// 16 .. 256. A negs entry outside [0, V) is a hole (skipped, never read); a
+// label equal to `ignore` or outside [0, V) ignores the token. Non-hole
+// negatives are distinct and ascending (the caller's promise; the order lets a
+// label that is also a negative find its row). A negative equal to a token's
+// label is not a negative of that token. order[N]: token indices with equal
+// labels adjacent, ascending inside a run (read only with dW). beta weighs the
+// positive's term (1: BCE; gBCE: 1 - t (1 - alpha)). dW / db: the rows named by
+// a valid negative or a valid token's label are assigned, every other row is
+// left as it was. linear_xent_splits also forces the negative splits of pass1.
+struct LinearBceRowsArgs {
+  const float* H;          // [N, E]
+  const float* W;          // [V, E]
+  const float* bias;       // [V]
+  const int64_t* labels;   // [N]
+  const int32_t* order;    // [N]
+  const int64_t* negs;     // [S]
+  int N; int S; int64_t V; int64_t ignore; float beta;
+  float* dH;               // [N, E] (scaled by 1/n_valid; zeros for ignored tokens)
+  float* lossv;            // [N] per-token loss (0 for ignored)
+  float* dW; float* db;    // optional [V, E], [V]
+  float* loss;             // optional scalar: sum(lossv) / max(1, n_valid)
+  double* loss_acc;        // optional running sum: += loss (device, fp64)
+  void* workspace;
+};
+size_t linear_bce_rows_workspace(int N, int S, int E);
+void linear_bce_rows(const LinearBceRowsArgs& a, int E, hipStream_t s);
+
 // -------------------------------------------------------- attention ----
 // Fused small-T MHA core (attention.hip): qkv [B,T,3E] fp32 (q|k|v, each
 // H x dk), key-padding mask from ids != pad_id, dropout(rate) from a counter

@@ -6,7 +6,8 @@ published BERT4Rec one: --max-len 200 --embed-dim 64 (T > 64 runs the tiled
 attention and wide LayerNorm kernels; the fused block covers T <= 64).
 --causal trains the next-item (causal attention) model on shifted labels.
 --negatives S trains with the sampled-softmax loss over S shared negatives
-(0: the full softmax)."""
+(0: the full softmax); --loss bce --negatives S with BCE against them, gBCE
+with --gbce-t t."""
 import argparse
 import json
 import sys
@@ -34,6 +35,10 @@ def main():
                     help="causal attention, per-position input block, labels = the next item")
     ap.add_argument("--negatives", type=int, default=0,
                     help="sampled softmax over this many shared negatives (0: full softmax)")
+    ap.add_argument("--loss", choices=("full", "sampled", "bce"), default=None,
+                    help="training loss (default: sampled when --negatives is given, else full)")
+    ap.add_argument("--gbce-t", type=float, default=0.0,
+                    help="--loss bce: gBCE calibration t in [0, 1] (0: plain BCE)")
     ap.add_argument("--torch-encoder", action="store_true",
                     help="torch reference attention/LayerNorm instead of the HIP kernels")
     a = ap.parse_args()
@@ -43,8 +48,11 @@ def main():
     dev = "cuda"
     T = a.max_len
     ckw = {"causal": True} if a.causal else {}
-    if a.negatives:
-        ckw.update(loss="sampled", num_negatives=a.negatives)
+    loss = a.loss or ("sampled" if a.negatives else "full")
+    if loss != "full":
+        ckw.update(loss=loss, num_negatives=a.negatives)
+    if loss == "bce":
+        ckw.update(gbce_t=a.gbce_t)
     tr = Bert4RecTrainer(a.items, T, a.embed_dim, a.heads, a.layers, a.batch, device=dev, **ckw)
     g = torch.Generator(device=dev).manual_seed(0)
     pool = []
@@ -74,7 +82,7 @@ def main():
     print(json.dumps({"model": "bert4rec", "batch": a.batch, "vocab": a.items + 2,
                       "max_len": T, "embed_dim": a.embed_dim, "heads": a.heads,
                       "layers": a.layers, "causal": a.causal,
-                      "negatives": a.negatives,
+                      "loss_kind": loss, "negatives": a.negatives, "gbce_t": a.gbce_t,
                       "graph": not a.no_graph, "fused_encoder": not a.torch_encoder, "ms_per_step": round(el / a.steps * 1e3, 4),
                       "sequences_per_sec": round(a.batch * a.steps / el, 1),
                       "loss": round(tr.pop_loss(), 4)}))

@@ -71,8 +71,9 @@ class Config:
     mask_prob: float = 0.2
     model_parallel: bool = False
     objective: str = "masked"         # bert4rec: masked (BERT4Rec) | next_item (causal, SASRec-style)
-    train_loss: str = "full"          # bert4rec: full (softmax over the catalogue) | sampled_softmax
-    num_negatives: int = 0            # sampled_softmax: shared uniform negatives per step (>= 1)
+    train_loss: str = "full"          # bert4rec: full (softmax over the catalogue) | sampled_softmax | bce
+    num_negatives: int = 0            # sampled_softmax / bce: shared uniform negatives per step (>= 1)
+    gbce_t: float = 0.0               # bce: gBCE calibration t in [0, 1] (0: plain BCE)
     # derived
     size_map: Dict[str, int] = field(default_factory=dict)
     # ---- new (optional) keys
@@ -165,15 +166,19 @@ def validate(cfg: Config) -> None:
         raise ValueError(f"objective must be masked|next_item, got {cfg.objective!r}")
     if cfg.objective == "next_item" and cfg.model != "bert4rec":
         raise ValueError("objective = next_item is supported by the bert4rec model only")
-    if cfg.train_loss not in ("full", "sampled_softmax"):
-        raise ValueError(f"train_loss must be full|sampled_softmax, got {cfg.train_loss!r}")
-    if cfg.train_loss == "sampled_softmax":
+    if cfg.train_loss not in ("full", "sampled_softmax", "bce"):
+        raise ValueError(f"train_loss must be full|sampled_softmax|bce, got {cfg.train_loss!r}")
+    if cfg.train_loss != "full":
         if cfg.model != "bert4rec":
-            raise ValueError("train_loss = sampled_softmax is supported by the bert4rec model only")
+            raise ValueError(f"train_loss = {cfg.train_loss} is supported by the bert4rec model only")
         if cfg.num_negatives < 1:
-            raise ValueError("train_loss = sampled_softmax needs num_negatives >= 1")
+            raise ValueError(f"train_loss = {cfg.train_loss} needs num_negatives >= 1")
     elif cfg.num_negatives < 0:
         raise ValueError("num_negatives must be >= 0")
+    if not 0.0 <= cfg.gbce_t <= 1.0:
+        raise ValueError(f"gbce_t must be in [0, 1], got {cfg.gbce_t}")
+    if cfg.gbce_t != 0.0 and cfg.model != "bert4rec":
+        raise ValueError("gbce_t is supported by the bert4rec model only")
     if cfg.table_dtype not in ("fp32", "bf16"):
         raise ValueError(f"table_dtype must be fp32|bf16, got {cfg.table_dtype!r}")
     if cfg.table_dtype == "bf16" and cfg.model not in ("dlrm", "dcnv2"):

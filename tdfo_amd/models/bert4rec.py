@@ -34,7 +34,10 @@ every shape (encoder.hip's fused block has no causal form).
 ``Bert4RecTrainer(loss="sampled", num_negatives=S)`` trains either model with
 a sampled softmax: every position against its positive and S uniform negatives
 shared by the batch (``ops.sample_ids`` / ``ops.xent_candidates`` /
-``sampled_linear_cross_entropy`` on ``tdfo::linear_xent_rows``). The output
+``sampled_linear_cross_entropy`` on ``tdfo::linear_xent_rows``), and
+``loss="bce", gbce_t=t`` with binary cross-entropy / gBCE against the same kind
+of negatives (``ops.bce_candidates`` / ``sampled_linear_bce`` on
+``tdfo::linear_bce_rows``; label smoothing does not apply to it). The output
 layer's gradient is then dense in the flat buffer, zero outside the candidates,
 and the flat optimizer steps it; eval and checkpoints are the same.
 """
@@ -523,6 +526,51 @@ def sampled_linear_cross_entropy(H, W, b, cand, target, eps=0.1, loss_acc=None, 
                                 loss_acc, unit_grad)
 
 
+class _SampledBceFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, H, W, b, labels, order, negs, beta, ignore, loss_acc, unit_grad):
+        N = H.shape[0]
+        dH = torch.empty_like(H)
+        lossv = torch.empty(N, dtype=torch.float32, device=H.device)
+        # as _SampledXentFn: with a unit gradient the kernel writes the
+        # negatives' and labels' rows straight into the (zeroed) .grad buffers
+        direct = bool(unit_grad and W.grad is not None and b.grad is not None and
+                      W.grad.is_contiguous() and b.grad.is_contiguous())
+        dW = W.grad if direct else torch.zeros_like(W)
+        db = b.grad if direct else torch.zeros_like(b)
+        loss = torch.empty(1, dtype=torch.float32, device=H.device)
+        ops.linear_bce_rows(H, W, b, labels, order, negs, beta, ignore, dH, lossv, dW, db,
+                            loss=loss, loss_acc=loss_acc)
+        ctx.save_for_backward(dH, dW, db)
+        ctx.unit_grad = unit_grad
+        ctx.direct = direct
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        dH, dW, db = ctx.saved_tensors
+        none = (None,) * 7
+        if ctx.unit_grad:      # caller's promise: the loss is backward()'s root (g == 1)
+            if ctx.direct:
+                return (dH, None, None) + none
+            return (dH, dW, db) + none
+        return (dH * g, dW * g, db * g) + none
+
+
+def sampled_linear_bce(H, W, b, labels, order, negs, beta=1.0, ignore=PAD_ID, loss_acc=None,
+                       unit_grad=False):
+    """mean BCE / gBCE of every token against its positive row W[labels[n]] and
+    the shared negative rows W[negs] (ops.linear_bce_rows: negs holds holes,
+    order the token indices sorted by label; ops.bce_candidates builds both),
+    fused. beta weighs the positive's term (1: BCE). Label smoothing does not
+    apply to this loss. loss_acc / unit_grad as in sampled_linear_cross_entropy:
+    with unit_grad and existing contiguous W.grad / b.grad (zeroed by the
+    caller) the kernel writes the named rows there; the gradient is exactly
+    zero everywhere else."""
+    return _SampledBceFn.apply(H.contiguous(), W, b, labels.contiguous(), order.contiguous(),
+                               negs.contiguous(), float(beta), int(ignore), loss_acc, unit_grad)
+
+
 class Bert4Rec(nn.Module):
     """Reference parameter names are preserved (state_dict() keys match
     torchrec's Bert4Rec except the item table, exported by the trainer)."""
@@ -608,16 +656,25 @@ class Bert4RecTrainer:
                  n_layers: int = 2, batch_size: int = 16, lr: float = 3e-4, wd: float = 1e-4,
                  device="cpu", mode: str = "local", group=None, rank: int = 0, world: int = 1,
                  dropout: float = 0.1, seed: int = 42, label_smoothing: float = 0.1,
-                 causal: bool = False, loss: str = "full", num_negatives: int = 0):
+                 causal: bool = False, loss: str = "full", num_negatives: int = 0,
+                 gbce_t: float = 0.0):
         self.V = n_items + 2                     # 0 = PAD, n_items + 1 = MASK
-        if loss not in ("full", "sampled"):
-            raise ValueError(f"loss must be 'full' or 'sampled', got {loss!r}")
-        if loss == "sampled" and not 1 <= num_negatives <= n_items:
-            raise ValueError(f"loss='sampled' needs 1 <= num_negatives <= n_items = {n_items}, "
+        if loss not in ("full", "sampled", "bce"):
+            raise ValueError(f"loss must be 'full', 'sampled' or 'bce', got {loss!r}")
+        if loss != "full" and not 1 <= num_negatives <= n_items:
+            raise ValueError(f"loss={loss!r} needs 1 <= num_negatives <= n_items = {n_items}, "
                              f"got {num_negatives}")
+        if not 0.0 <= gbce_t <= 1.0:
+            raise ValueError(f"gbce_t must be in [0, 1], got {gbce_t}")
         # "sampled": every position against its positive and num_negatives
-        # shared uniform negatives (sampled softmax) instead of the catalogue
-        self.loss_kind, self.S = loss, int(num_negatives) if loss == "sampled" else 0
+        # shared uniform negatives (sampled softmax) instead of the catalogue;
+        # "bce": binary cross-entropy against the same kind of negatives, the
+        # positive's term weighed by beta = 1 - gbce_t (1 - alpha), alpha =
+        # min(1, S / (n_items - 1)) (gBCE; gbce_t = 0: plain BCE). Label
+        # smoothing does not apply to "bce" (label_smoothing is not used)
+        self.loss_kind, self.S = loss, int(num_negatives) if loss != "full" else 0
+        alpha = min(1.0, self.S / max(1, n_items - 1))
+        self.beta = 1.0 - float(gbce_t) * (1.0 - alpha)
         self.T, self.E, self.B = max_len, embed_dim, batch_size
         self.causal = bool(causal)               # next-item objective (module docstring)
         self.device = dev = torch.device(device)
@@ -680,8 +737,13 @@ class Bert4RecTrainer:
             # the step's negatives, candidate list (labels + negatives, holes
             # -1) and every token's slot in it: static buffers
             self.neg = torch.zeros(self.S, dtype=torch.int64, device=dev)
-            self.cand = torch.full((ntok + self.S,), -1, dtype=torch.int64, device=dev)
-            self.cand_target = torch.full((ntok,), -1, dtype=torch.int64, device=dev)
+            if loss == "bce":
+                # the sorted negatives (repeats -1) and the token order by label
+                self.negs = torch.full((self.S,), -1, dtype=torch.int64, device=dev)
+                self.order = torch.zeros(ntok, dtype=torch.int32, device=dev)
+            else:
+                self.cand = torch.full((ntok + self.S,), -1, dtype=torch.int64, device=dev)
+                self.cand_target = torch.full((ntok,), -1, dtype=torch.int64, device=dev)
             self._neg_seed = (seed * 0x9E3779B1 + rank * 0x85EBCA77 + 0x5A3D9E1) & 0xFFFFFFFF
         self.loss_sum = torch.zeros(1, dtype=torch.float64, device=dev)
         self.steps = 0
@@ -768,6 +830,13 @@ class Bert4RecTrainer:
             # negatives uniform over the items 1 .. n_items (PAD / MASK never),
             # keyed by (seed, rank, rng_step): fresh in every replayed step
             ops.sample_ids(self._neg_seed, self.model.rng_step, 1, self.V - 1, self.neg)
+        if self.loss_kind == "bce":
+            ops.bce_candidates(labels.reshape(-1), self.neg, PAD_ID, self.negs, self.order)
+            loss = sampled_linear_bce(h.reshape(-1, self.E), self.model.out.weight,
+                                      self.model.out.bias, labels.reshape(-1), self.order,
+                                      self.negs, self.beta, PAD_ID, loss_acc=self.loss_sum,
+                                      unit_grad=True)
+        elif self.S:
             ops.xent_candidates(labels.reshape(-1), self.neg, PAD_ID, self.cand, self.cand_target)
             loss = sampled_linear_cross_entropy(h.reshape(-1, self.E), self.model.out.weight,
                                                 self.model.out.bias, self.cand, self.cand_target,

@@ -975,6 +975,54 @@ def xent_candidates(labels, neg, ignore, cand, target):
     target.copy_(pos.masked_fill(ign, -1))
 
 
+def linear_bce_rows(H, W, bias, labels, order, negs, beta, ignore, dH, lossv, dW=None, db=None,
+                    loss=None, loss_acc=None):
+    """Linear + BCE / gBCE of every token against its positive row W[labels[n]]
+    and the shared negative rows W[negs], fwd+bwd, no [N, S] logits
+    (csrc/kernels/linear_bce_rows.hip; E in 16 / 32 / 64 / 128 / 256 on the GPU):
+    loss_n = (beta softplus(-zy) + sum_c softplus(z_c)) / (K + 1) over the K
+    valid negatives that are not the token's label; beta = 1 is BCE, gBCE sets
+    beta = 1 - t (1 - alpha). labels int64 [N]: ``ignore`` or an id outside
+    [0, V) ignores the token. negs int64 [S]: an entry outside [0, V) is a
+    hole (skipped, never read); the other entries must be distinct and
+    ascending. order int32 [N]: token indices with equal labels adjacent,
+    ascending inside a run (``bce_candidates`` builds both). dH / lossv are
+    written for every token (zeros for ignored ones); dW / db only in the rows
+    named by a valid negative or a valid token's label (assigned; every other
+    row keeps what it held). loss / loss_acc as in linear_xent. N == 0 or
+    S == 0: nothing is written."""
+    if _gpu(H):
+        _native().linear_bce_rows(H, W, bias, labels, order, negs, float(beta), int(ignore), dH,
+                                  lossv, dW, db, loss, loss_acc)
+    elif H.shape[0] and negs.numel():
+        nv = ref.linear_bce_rows(H, W, bias, labels, negs, beta, ignore, dH, lossv, dW, db)
+        if loss is not None:
+            loss.view(-1)[0] = lossv.sum() / max(1, nv)
+            if loss_acc is not None:
+                loss_acc.view(-1)[0] += loss.view(-1)[0].double()
+
+
+def bce_candidates(labels, neg, ignore, negs, order):
+    """Negatives and label order of one BCE step for ``linear_bce_rows``:
+    negs [S] = the sorted negatives, every repeated entry and every id outside
+    [0, 2^31 - 1) a hole (-1); order [N] (int32) = the token indices stably
+    sorted by label, ignored tokens last. Static shapes, no host sync
+    (graph-capturable)."""
+    labels, neg = labels.reshape(-1), neg.reshape(-1)
+    oor = (neg < 0) | (neg >= _CAND_SENT)
+    sk, _ = sort_pairs(neg.masked_fill(oor, _CAND_SENT),
+                       torch.arange(neg.numel(), dtype=torch.int32, device=neg.device),
+                       _CAND_BITS)
+    hole = sk == _CAND_SENT
+    hole[1:] |= sk[1:] == sk[:-1]
+    negs.copy_(sk.masked_fill(hole, -1))
+    ign = (labels == ignore) | (labels < 0) | (labels >= _CAND_SENT)
+    _, tok = sort_pairs(labels.masked_fill(ign, _CAND_SENT),
+                        torch.arange(labels.numel(), dtype=torch.int32, device=labels.device),
+                        _CAND_BITS)
+    order.copy_(tok)
+
+
 def jagged_to_dense(values, offsets, T, pad, out):
     """values [nnz, D] fp32 + offsets [B+1] -> out [B, T, D] (pad fill)."""
     if _gpu(values):

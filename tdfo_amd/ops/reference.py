@@ -670,6 +670,45 @@ def linear_xent_rows(H, W, bias, cand, target, eps, dH, lossv, dW=None, db=None,
     return nv
 
 
+def linear_bce_rows(H, W, bias, labels, negs, beta, ignore, dH, lossv, dW=None, db=None):
+    """Oracle of the shared-negative Linear+BCE / gBCE: every token against its
+    positive row W[labels[n]] (weight beta) and the valid rows W[negs], a
+    negative equal to the token's label left out, the token's terms divided by
+    their number (K + 1), mean over the non-ignored tokens. A negs entry
+    outside [0, V) is a hole; a label equal to ``ignore`` or outside [0, V)
+    ignores the token. dW / db: only the rows named by valid negatives or valid
+    labels are assigned (every other row keeps what it held).
+    Returns the number of valid tokens."""
+    V = W.shape[0]
+    rows = negs[(negs >= 0) & (negs < V)]
+    tok = torch.nonzero((labels != ignore) & (labels >= 0) & (labels < V)).view(-1)
+    nv = int(tok.numel())
+    lossv.zero_()
+    dH.zero_()
+    if nv == 0:                         # (nothing valid: dW / db are not written)
+        return nv
+    y = labels[tok]
+    sp = torch.nn.functional.softplus
+    with torch.enable_grad():
+        Hr = H.detach().float().clone().requires_grad_(True)
+        Wr = W.detach().float().clone().requires_grad_(True)
+        br = bias.detach().float().clone().requires_grad_(True)
+        Hv = Hr[tok]
+        z = Hv @ Wr[rows].t() + br[rows]
+        zy = (Hv * Wr[y]).sum(1) + br[y]
+        keep = rows.view(1, -1) != y.view(-1, 1)           # the label is not its own negative
+        k1 = keep.sum(1).to(z.dtype) + 1.0
+        per = (beta * sp(-zy) + (sp(z) * keep).sum(1)) / k1
+        (per.sum() / nv).backward()
+    lossv[tok] = per.detach()
+    dH.copy_(Hr.grad)
+    if dW is not None:
+        named = torch.unique(torch.cat([rows, y]))
+        dW[named] = Wr.grad[named]
+        db[named] = br.grad[named]
+    return nv
+
+
 def sample_ids(seed, step, lo, hi, out):
     """Python mirror of the GPU sampler: out[i] = lo + ((hash3(seed, step mod
     2^32, i) * (hi - lo)) >> 32), the counter hash of tdfo_common.h."""

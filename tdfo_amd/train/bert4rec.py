@@ -66,8 +66,8 @@ def run(cfg: Config, out_dir: str = ".", device: Optional[str] = None) -> List[D
     tr = Bert4RecTrainer(n_items, cfg.max_len, cfg.embed_dim, cfg.n_heads, cfg.n_layers, B,
                          cfg.learning_rate, cfg.weight_decay, dev, mode, group, rank, world,
                          seed=cfg.seed, causal=causal,
-                         loss="sampled" if cfg.train_loss == "sampled_softmax" else "full",
-                         num_negatives=cfg.num_negatives)
+                         loss={"sampled_softmax": "sampled"}.get(cfg.train_loss, cfg.train_loss),
+                         num_negatives=cfg.num_negatives, gbce_t=cfg.gbce_t)
     data_dev = dev if cfg.data_on_device else torch.device("cpu")
     train = DeviceColumns({"seqs": train_cols["train_interactions"].astype("int64"),
                            "labels": train_cols["labels"].astype("int64")}, data_dev)
