@@ -170,6 +170,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x
 // the [blocks][3n] partial buffer + reduce_rows of the narrow path, which
 // would be tens of MB here; `part` is unused.
 constexpr int LNW_THREADS = 64 * LN_WAVES;
+constexpr int LNW_CHUNK = 32;               // rows per partial sum of the column pass
 
 // sum over the workgroup, the same value in every thread: wave sums, then the
 // waves in order
@@ -260,14 +261,25 @@ __global__ __launch_bounds__(LNW_THREADS) void ln_wide_col_kernel(
   if (e >= n) return;
   const uint32_t sd = PRO ? pro_seed(pa) : 0u;
   const float pe = PRO ? pa.pos[e] : 0.f;
+  // Rows in ascending order, in chunks of LNW_CHUNK whose sums are then added
+  // up: one chain over M = 1030 rows carried 1030 roundings at the running
+  // total's size (dbeta 11.5 x the reference's error); chunked, each of the
+  // two levels carries 32. M <= LNW_CHUNK is the single chain it was.
   float dg = 0.f, db = 0.f, dp = 0.f;
+  for (int64_t r0 = 0; r0 < M; r0 += LNW_CHUNK) {
+    const int64_t r1 = r0 + LNW_CHUNK < M ? r0 + LNW_CHUNK : M;
+    float cg = 0.f, cb = 0.f, cp = 0.f;
 #pragma unroll 4
-  for (int64_t r = 0; r < M; ++r) {
-    const float gv = PRO ? g[r * n + e] * pro_mul(pa, sd, r, e) : g[r * n + e];
-    const float xh = (x[r * n + e] + pe - mean[r]) * rstd[r];
-    dg += gv * xh;
-    db += gv;
-    if (PRO) dp += dx[r * n + e];
+    for (int64_t r = r0; r < r1; ++r) {
+      const float gv = PRO ? g[r * n + e] * pro_mul(pa, sd, r, e) : g[r * n + e];
+      const float xh = (x[r * n + e] + pe - mean[r]) * rstd[r];
+      cg += gv * xh;
+      cb += gv;
+      if (PRO) cp += dx[r * n + e];
+    }
+    dg += cg;
+    db += cb;
+    dp += cp;
   }
   out[idx ? idx[e] : e] = dg;
   out[idx ? idx[n + e] : n + e] = db;

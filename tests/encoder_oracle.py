@@ -1,8 +1,9 @@
 """float64 oracles of the Bert4Rec encoder kernels and the shared cases of
 their tests: the counter-hash dropout masks, LayerNorm and the sequence
-prologue, the multi-head attention core, and the fused pre-norm transformer
-block (forward with its four saved intermediates, backward with dx and the 12
-parameter gradients).
+prologue, the multi-head attention core (with the row log-sum-exp the tiled
+kernels save, and the hard input families of their cases), and the fused
+pre-norm transformer block (forward with its four saved intermediates,
+backward with dx and the 12 parameter gradients).
 
 Everything is written out by hand in float64 without autograd and without
 ``tdfo_amd.ops.reference`` (tests/test_encoder_oracle.py checks the backwards
@@ -147,7 +148,9 @@ def _heads(t, H):
     return t.view(B, T, H, E // H).permute(0, 2, 1, 3)          # [B, H, T, dk]
 
 
-def _attn_probs(qkv, valid, H, causal):
+def _masked_scores(qkv, valid, H, causal):
+    """-> q, k, v [B, H, T, dk], the masked scores [B, H, T, T] and the mask of
+    the keys that carry a gradient (visible and not PAD)"""
     B, T, E3 = qkv.shape
     E = E3 // 3
     q, k, v = (_heads(qkv[..., i * E:(i + 1) * E], H) for i in range(3))
@@ -158,9 +161,23 @@ def _attn_probs(qkv, valid, H, causal):
         see = torch.ones(T, T, dtype=torch.bool).tril()
         s = torch.where(see, s, torch.full_like(s, -math.inf))
         keym = keym & see
+    return q, k, v, s, keym
+
+
+def _attn_probs(qkv, valid, H, causal):
+    q, k, v, s, keym = _masked_scores(qkv, valid, H, causal)
     s = s - s.max(-1, keepdim=True).values
     e = torch.exp(s)
     return q, k, v, e / e.sum(-1, keepdim=True), keym
+
+
+def mha_lse(qkv, valid, H, causal=False):
+    """[B, H, T] log-sum-exp of the masked scores: PAD keys at -1e9, future
+    keys excluded, no dropout (a row whose visible keys are all PAD: -1e9 +
+    log of their number)"""
+    _, _, _, s, _ = _masked_scores(qkv.to(F64), valid, H, causal)
+    mx = s.max(-1).values
+    return mx + torch.log(torch.exp(s - mx[..., None]).sum(-1))
 
 
 def mha_fwd(qkv, valid, H, m, causal=False):
@@ -308,9 +325,53 @@ ATTN_SHAPES = [(2, 64, 16, 4), (2, 33, 16, 4), (2, 1, 8, 2), (2, 2, 16, 2), (3, 
                (2, 64, 64, 2), (2, 64, 64, 1), (2, 63, 128, 2)]
 ATTN_CASES = [s + (0.0, p) for s in ATTN_SHAPES for p in PATTERNS]
 ATTN_CASES += [(2, 64, 16, 4, 0.25, "left"), (2, 64, 64, 1, 0.25, "left")]
+# tiled attention (attention_long.hip, 64 < T <= 512): B = 2, H = 2, E = 2 d_k
+LONG_DK = (4, 8, 16, 32, 64)
+LONG_FAMILIES = ("randn", "peaked", "rising", "falling")
+LONG_TILE = 64
+# every operand width (d_k 4: scalar, 8: float2, >= 16: float4) and column-block
+# count (1, 2, 4) at one key past a tile, whole tiles, one past two tiles, one
+# short of the maximum and the maximum; five more T at one d_k each
+LONG_EDGE_SHAPES = [(2, T, 2 * dk, 2) for dk in LONG_DK for T in (65, 128, 129, 511, 512)]
+LONG_EDGE_SHAPES += [(2, T, 2 * dk, 2) for T, dk in zip((127, 192, 193, 320, 449), LONG_DK)]
+# causal grids B * H * nt (forward) and twice that (backward) that are no
+# multiple of 8: the blocks past the last whole group of 8 keep their index
+LONG_TAIL_SHAPES = [(3, 65, 8, 1), (1, 200, 32, 1), (3, 129, 12, 3), (3, 129, 48, 3),
+                    (1, 65, 64, 1)]
+LONG_DROP_SHAPES = [(2, 129, 16, 4), (2, 200, 64, 2), (1, 512, 64, 1)]
+LONG_PAD7_SHAPE = (2, 129, 16, 2)
+# (B, T, E, H, rate, pattern, causal, family, pad_id)
+LONG_CASES = [s + (0.0, p, c, "randn", 0) for s in LONG_EDGE_SHAPES for p in PATTERNS
+              for c in (False, True)]
+LONG_HARD_CASES = [(2, T, 2 * dk, 2, 0.0, p, c, f, 0) for f in LONG_FAMILIES[1:]
+                   for T in (129, 512) for dk in LONG_DK for p in ("left", "none")
+                   for c in (False, True)]
+LONG_CASES += LONG_HARD_CASES
+LONG_CASES += [s + (r, "left", c, "randn", 0) for s in LONG_DROP_SHAPES for r in (0.1, 0.5)
+               for c in (False, True)]
+LONG_CASES += [s + (0.0, "left", c, "randn", 0) for s in LONG_TAIL_SHAPES for c in (False, True)]
+LONG_CASES += [LONG_PAD7_SHAPE + (0.0, "left", c, "randn", 7) for c in (False, True)]
+# block order: the causal grid-tail cases and the paper shape
+LONG_ORDER_CASES = [s + (0.0, "left", True, "randn", 0)
+                    for s in LONG_TAIL_SHAPES + [(2, 200, 64, 2)]]
+LONG_PEAK = 2.5          # "peaked": the q and k thirds times this
+LONG_RAMP = 6.0          # "rising" / "falling": a = LONG_RAMP * d_k^(1/4)
+LONG_SCORE_RANGE = (20.0, 80.0)
+
 LN_N = (1, 2, 63, 64, 65, 128, 129, 255, 256, 257, 512, 513, 1023, 1024, 1025, 3200)
 LN_CASES = [(M, n) for n in LN_N for M in (1, 3, 5)] + [(1030, n) for n in (16, 320, 1024)]
 LN_FAMILIES = ("randn", "mean100", "const")
+# the wide path (ln_wide_*, 1024 < n <= 32768): the maximum width and one short
+# of it, the paper's n = T E = 12800, n around a multiple of the 256-thread
+# stride, and 1030 rows in the column pass. These sizes test indexing, not the
+# variance formula (mean100 reaches the wide kernels at n = 1025 and 3200).
+LN_WIDE_CASES = [(2, 32768), (2, 32767), (3, 12800), (3, 1279), (3, 1280), (3, 1281),
+                 (1030, 1025)]
+LN_CASES += LN_WIDE_CASES
+
+
+def ln_families(M, n):
+    return ("randn", "const") if (M, n) in LN_WIDE_CASES else LN_FAMILIES
 PRO_RATES = (0.0, 0.1, 0.5)
 # The constant row: variance 0, so rstd = eps^-1/2 = 316 multiplies whatever
 # rounding the fp32 row mean carries (up to an ulp of the constant, e.g. from
@@ -392,6 +453,91 @@ def attn_case(B, T, E, H, rate, pattern, causal):
                            dout=dout, ids=ids, valid=valid, m=m, seed=SEED, step=STEP, exact=exact)
 
 
+def score_stats(qkv, H):
+    """float64 scores q.k / sqrt(d_k) of every (query, key) pair, no mask ->
+    (max |score|, [per 64-key tile: mean over all rows of the tile's maximum],
+    fraction of the rows whose maximum lies in the last tile)"""
+    qkv = qkv.to(F64)
+    E = qkv.shape[-1] // 3
+    q, k = _heads(qkv[..., :E], H), _heads(qkv[..., E:2 * E], H)
+    s = q @ k.transpose(-1, -2) / math.sqrt(E // H)
+    tmax = torch.stack([t.max(-1).values for t in s.split(LONG_TILE, -1)], -1)
+    last = float((tmax.argmax(-1) == tmax.shape[-1] - 1).double().mean())
+    return float(s.abs().max()), [float(v) for v in tmax.reshape(-1, tmax.shape[-1]).mean(0)], last
+
+
+def family_ok(family, T, smax, tiles, last):
+    """The conditions a hard input family is there for: max |score| within
+    LONG_SCORE_RANGE, and for "rising" ("falling") the mean over rows of the
+    tile's maximum score increases (decreases) from each 64-key tile to the
+    next. A partial last tile is held to the same for "falling". For "rising"
+    it cannot be: at T = 129 its one key carries the ramp's top, 36 * 128 / 129,
+    but the tile before takes the maximum over 64 keys of ramp + noise (the
+    terms q0.k0 and a u.k0 / sqrt(d_k), sigma 2.3 to 4.4), about 4 above the
+    ramp, at every a that keeps max |score| under 80. What that tile is there
+    for is a rescale in the last, partial tile, so it is required to hold the
+    row's overall maximum in at least one row in 16 (``last`` is that
+    fraction)."""
+    lo, hi = LONG_SCORE_RANGE
+    if not lo <= smax <= hi:
+        return False
+    full = T // LONG_TILE
+    steps = [b - a for a, b in zip(tiles, tiles[1:])]
+    if family == "rising":
+        return all(d > 0 for d in steps[:full - 1]) and (T % LONG_TILE == 0 or last >= 1 / 16)
+    if family == "falling":
+        return all(d < 0 for d in steps)
+    return True
+
+
+@functools.lru_cache(maxsize=None)
+def long_attn_case(B, T, E, H, rate, pattern, causal, family, pad_id=0):
+    """CPU fp32 inputs and the fp64 oracle (out, dqkv, lse) of one case of the
+    tiled attention kernels. Families: "randn"; "peaked", the q and k thirds
+    times LONG_PEAK; "rising", a unit vector u per head, a (j / T) u added to
+    key j and a u to every query, a = LONG_RAMP d_k^(1/4), so the scores climb
+    by a^2 / sqrt(d_k) = 36 along the keys, the winning keys sit in the last
+    tiles and the online softmax rescales by a small alpha at every tile;
+    "falling", the ramp reversed ((T - 1 - j) / T), so every later tile adds
+    terms that underflow against the running max. A hard family walks at most
+    16 seeds for inputs that meet family_ok (at d_k = 4 the ramp's noise term
+    a u.k0 / sqrt(d_k) is shared by all rows of a head and can reorder two
+    neighbouring tiles): a condition on the inputs. Cached: read-only."""
+    dk = E // H
+    base = 1000 * T + 10 * E + H + 7 * PATTERNS.index(pattern) \
+        + 100003 * LONG_FAMILIES.index(family) + 1009 * pad_id
+    for walk in range(16):
+        g = torch.Generator().manual_seed(base * 16 + walk)
+        qkv = torch.randn(B, T, 3 * E, generator=g)
+        dout = torch.randn(B, T, E, generator=g)
+        ids = make_ids(B, T, pattern, g, pad_id)
+        if pad_id != 0:             # ids hold both 0 and pad_id: 0 is then an ordinary item
+            ids[B - 1, T - 1] = 0
+        if family == "peaked":
+            qkv[..., :2 * E] *= LONG_PEAK
+        elif family in ("rising", "falling"):
+            u = torch.randn(H, dk, generator=g)
+            u = (u / u.norm(dim=-1, keepdim=True)).reshape(1, 1, E)
+            a = LONG_RAMP * dk ** 0.25
+            j = torch.arange(T, dtype=torch.float32)
+            ramp = (j if family == "rising" else T - 1 - j) / T
+            qkv[..., :E] += a * u
+            qkv[..., E:2 * E] += a * ramp.view(1, T, 1) * u
+        smax, tiles, last = score_stats(qkv, H)
+        if family == "randn" or family_ok(family, T, smax, tiles, last):
+            break
+    else:
+        raise AssertionError(f"no seed of 16 meets the conditions of {family}: {smax} {tiles} {last}")
+    valid = ids != pad_id
+    m = mul(attn_keep(B, H, T, rate, SEED, STEP, stride=512), rate)
+    exact = dict(out=mha_fwd(qkv, valid, H, m, causal), dqkv=mha_bwd(qkv, valid, dout, H, m, causal),
+                 lse=mha_lse(qkv, valid, H, causal))
+    return SimpleNamespace(B=B, T=T, E=E, H=H, rate=rate, pattern=pattern, causal=causal,
+                           family=family, pad_id=pad_id, qkv=qkv, dout=dout, ids=ids, valid=valid,
+                           m=m, seed=SEED, step=STEP, smax=smax, tiles=tiles, last=last, walk=walk,
+                           exact=exact)
+
+
 @functools.lru_cache(maxsize=None)
 def ln_case(M, n, family, rate=None):
     """LayerNorm (rate None) or sequence-prologue case. Cached: read-only."""
@@ -434,11 +580,42 @@ def mean_err(got, mean, rstd):
     return float(((g - m).abs() / torch.maximum(m.abs(), 1.0 / rstd.reshape(-1))).max())
 
 
+LSE_UNIFORM = -5e8       # the tiled backward takes a row with lse below this for uniform
+LSE_UNIFORM_TOL = 32.0   # half an f32 ulp at 1e9
+
+
+def lse_err(got, exact):
+    """max |got - exact| / max(1, |exact|) over the rows that see a valid key.
+    The rows whose visible keys are all PAD (exact = -1e9 + log n) are left to
+    check_uniform_lse: through row_err(kind="elem") their 1e-3 * 1e9 would be
+    every ordinary row's denominator."""
+    g, e = got.detach().cpu().to(F64).reshape(-1), exact.reshape(-1)
+    assert g.shape == e.shape, (g.shape, e.shape)
+    if not bool(torch.isfinite(g).all()):
+        return math.inf
+    rows = e >= LSE_UNIFORM
+    if not bool(rows.any()):
+        return 0.0
+    return float(((g - e).abs() / e.abs().clamp_min(1.0))[rows].max())
+
+
+def check_uniform_lse(got, exact, what="lse"):
+    """rows whose visible keys are all PAD: below the backward's threshold and
+    within half an f32 ulp of the exact -1e9 + log n"""
+    g, e = got.detach().cpu().to(F64).reshape(-1), exact.reshape(-1)
+    rows = e < LSE_UNIFORM
+    bad = rows & ~((g < LSE_UNIFORM) & ((g - e).abs() <= LSE_UNIFORM_TOL))
+    assert not bool(bad.any()), f"{what}: {int(bad.sum())} of {int(rows.sum())} uniform rows off"
+
+
 def errs(got, exact):
     """{name: row_err} over the tensors of ``exact`` present in ``got``"""
-    out = {k: row_err(got[k], e, KINDS.get(k)) for k, e in exact.items() if k in got}
+    out = {k: row_err(got[k], e, KINDS.get(k)) for k, e in exact.items()
+           if k in got and k != "lse"}
     if "mean" in out:
         out["mean"] = mean_err(got["mean"], exact["mean"], exact["rstd"])
+    if "lse" in exact and "lse" in got:
+        out["lse"] = lse_err(got["lse"], exact["lse"])
     return out
 
 
@@ -467,10 +644,20 @@ def ref_run(case):
         return {k: v.detach() for k, v in out.items()}
     if hasattr(c, "qkv"):
         out, dqkv = torch.empty(c.B, c.T, c.E), torch.empty_like(c.qkv)
-        step = torch.tensor([c.step])
-        ref.attention_fwd(c.qkv, c.ids, c.H, c.rate, c.seed, step, 0, out, causal=c.causal)
-        ref.attention_bwd(c.qkv, c.ids, c.dout, c.H, c.rate, c.seed, step, 0, dqkv, causal=c.causal)
-        return dict(out=out, dqkv=dqkv)
+        step, pad = torch.tensor([c.step]), getattr(c, "pad_id", 0)
+        ref.attention_fwd(c.qkv, c.ids, c.H, c.rate, c.seed, step, pad, out, causal=c.causal)
+        ref.attention_bwd(c.qkv, c.ids, c.dout, c.H, c.rate, c.seed, step, pad, dqkv,
+                          causal=c.causal)
+        if "lse" not in c.exact:
+            return dict(out=out, dqkv=dqkv)
+        # fp32 log-sum-exp of the reference's own score maths (attention_core)
+        dk = c.E // c.H
+        q, k, _ = c.qkv.view(c.B, c.T, 3, c.H, dk).permute(2, 0, 3, 1, 4)
+        s = (q / math.sqrt(dk)) @ k.transpose(-2, -1)
+        s = s.masked_fill(~(c.ids != pad).view(c.B, 1, 1, c.T), -1e9)
+        if c.causal:
+            s = s.masked_fill(torch.ones(c.T, c.T, dtype=torch.bool).triu(1), float("-inf"))
+        return dict(out=out, dqkv=dqkv, lse=torch.logsumexp(s, -1))
     M, n = c.M, c.n
     y, mean, rstd, dx = torch.empty(M, n), torch.empty(M), torch.empty(M), torch.empty(M, n)
     if c.rate is None:
@@ -508,3 +695,5 @@ def assert_within(got, case, tag):
         if not v <= bound(re_[k]):
             bad.append((k, v, re_[k]))
     assert not bad, (tag, bad)
+    if "lse" in case.exact:
+        check_uniform_lse(got["lse"], case.exact["lse"], tag + " lse")

@@ -136,13 +136,175 @@ def test_reference_error_attention(case, causal):
 
 @pytest.mark.parametrize("M,n", eo.LN_CASES)
 def test_reference_error_layernorm(M, n):
-    for family in eo.LN_FAMILIES:
+    for family in eo.ln_families(M, n):
         for rate in (None,) + eo.PRO_RATES:
             e = eo.ref_err(eo.ln_case(M, n, family, rate))
             _show(f"fp32 reference M={M} n={n} {family} rate={rate}", e)
             assert all(math.isfinite(v) for v in e.values())
             if family != "mean100" and n > 2:    # (n = 2: dx cancels to O(eps); mean 100: 1e-5)
                 assert max(e["y"], e["rstd"], e["dx"]) < 2e-5
+
+
+def test_layernorm_wide_cases_present():
+    assert set(eo.LN_WIDE_CASES) <= set(eo.LN_CASES) and len(set(eo.LN_CASES)) == len(eo.LN_CASES)
+    assert {(2, 32768), (2, 32767), (3, 12800), (3, 1279), (3, 1280), (3, 1281),
+            (1030, 1025)} == set(eo.LN_WIDE_CASES)
+    assert all(eo.ln_families(M, n) == ("randn", "const") for M, n in eo.LN_WIDE_CASES)
+    assert all(eo.ln_families(M, n) == eo.LN_FAMILIES for M, n in eo.LN_CASES
+               if (M, n) not in eo.LN_WIDE_CASES)
+
+
+# ------------------------------------------------- tiled attention (T > 64)
+def _plain_lse(qkv, valid, H, causal):
+    B, T, E3 = qkv.shape
+    E = E3 // 3
+    q, k, _ = qkv.view(B, T, 3, H, E // H).permute(2, 0, 3, 1, 4)
+    s = (q @ k.transpose(-2, -1) / math.sqrt(E // H)).masked_fill(~valid.view(B, 1, 1, T), -1e9)
+    if causal:
+        s = s.masked_fill(torch.ones(T, T, dtype=torch.bool).triu(1), -math.inf)
+    return torch.logsumexp(s, -1)
+
+
+@pytest.mark.parametrize("causal", [False, True])
+@pytest.mark.parametrize("pattern", ["full", "lone"])
+def test_mha_lse_matches_logsumexp(pattern, causal):
+    c = eo.long_attn_case(2, 129, 16, 2, 0.0, pattern, causal, "randn")
+    want = _plain_lse(c.qkv.to(F64), c.valid, c.H, causal)
+    assert c.exact["lse"].shape == (2, 2, 129) and c.exact["lse"].dtype == F64
+    assert float((c.exact["lse"] - want).abs().max()) < 1e-6     # (ulp of 1e9 in fp64: 1.2e-7)
+    ordinary = want > eo.LSE_UNIFORM
+    assert float((c.exact["lse"] - want)[ordinary].abs().max()) < 1e-12
+    # sequence 0: every row uniform ("full"); its one valid key is the last, which every
+    # row sees ("lone"), under the causal mask the last row only
+    uni = c.exact["lse"][0] < eo.LSE_UNIFORM
+    if pattern == "full":
+        assert bool(uni.all())
+    else:
+        assert not bool(uni[:, -1].any()) and bool(uni[:, :-1].all()) == causal \
+            and bool(uni[:, :-1].any()) == causal
+    n = torch.arange(1, 130, dtype=F64) if causal else torch.full((129,), 129.0, dtype=F64)
+    if pattern == "full":
+        assert float((c.exact["lse"][0] - (-1e9 + torch.log(n))).abs().max()) < 1e-6
+
+
+@pytest.mark.parametrize("T", [65, 512])
+@pytest.mark.parametrize("rate", [0.1, 0.5])
+def test_long_attention_mask_equals_reference_bit_for_bit(T, rate):
+    """row key stride 512 above T = 64; B * H = 6 > 1 so the stride matters"""
+    keep = eo.attn_keep(3, 2, T, rate, eo.SEED, eo.STEP, stride=512)
+    r = ref.attn_keep_scale(3, 2, T, rate, eo.SEED, eo.STEP, "cpu")
+    assert torch.equal(keep, r != 0) and torch.equal(eo.mul(keep, rate).float(), r)
+    assert not torch.equal(keep, eo.attn_keep(3, 2, T, rate, eo.SEED, eo.STEP, stride=64))
+
+
+@pytest.mark.parametrize("causal", [False, True])
+@pytest.mark.parametrize("case", [(2, 129, 16, 4, 0.1, "left", "randn"),
+                                  (2, 129, 8, 2, 0.0, "left", "peaked"),
+                                  (2, 129, 32, 2, 0.0, "none", "rising"),
+                                  (2, 129, 128, 2, 0.0, "left", "falling")])
+def test_long_mha_bwd_matches_autograd(case, causal):
+    c = eo.long_attn_case(*case[:6], causal, case[6])
+    qkv = c.qkv.to(F64).requires_grad_(True)
+    out = _plain_mha(qkv, c.valid, c.H, c.m, causal)
+    (g,) = torch.autograd.grad(out, qkv, c.dout.to(F64))
+    assert _rel(c.exact["out"], out.detach()) < 1e-12
+    assert _rel(c.exact["dqkv"], g) < 1e-10
+    assert float((c.exact["lse"] - _plain_lse(qkv.detach(), c.valid, c.H, causal)).abs().max()) < 1e-6
+
+
+def test_long_case_lists():
+    """every case the tiled-attention test is to run is in LONG_CASES, once"""
+    L = eo.LONG_CASES
+    assert len(set(L)) == len(L)
+    for dk in eo.LONG_DK:
+        for T in (65, 128, 129, 511, 512):
+            for p in eo.PATTERNS:
+                for causal in (False, True):
+                    assert (2, T, 2 * dk, 2, 0.0, p, causal, "randn", 0) in L
+        for fam in ("peaked", "rising", "falling"):
+            for T in (129, 512):
+                for p in ("left", "none"):
+                    for causal in (False, True):
+                        assert (2, T, 2 * dk, 2, 0.0, p, causal, fam, 0) in L
+    extra = {(T, E // 2) for B, T, E, H in eo.LONG_EDGE_SHAPES if T in (127, 192, 193, 320, 449)}
+    assert {T for T, _ in extra} == {127, 192, 193, 320, 449}
+    assert {dk for _, dk in extra} == set(eo.LONG_DK)
+    for causal in (False, True):
+        for s in [(2, 129, 16, 4), (2, 200, 64, 2), (1, 512, 64, 1)]:
+            for r in (0.1, 0.5):
+                assert s + (r, "left", causal, "randn", 0) in L
+        for s in [(3, 65, 8, 1), (1, 200, 32, 1), (3, 129, 12, 3), (3, 129, 48, 3), (1, 65, 64, 1)]:
+            assert s + (0.0, "left", causal, "randn", 0) in L
+        assert (2, 129, 16, 2, 0.0, "left", causal, "randn", 7) in L
+    # the causal grids of the tail shapes: B * H * nt forward, twice that backward; no forward
+    # grid is a multiple of 8, and the backward grids have tails of 4, 0, 6, 6 and 4 blocks
+    grids = [B * H * -(-T // 64) for B, T, E, H in eo.LONG_TAIL_SHAPES]
+    assert grids == [6, 4, 27, 27, 2] and all(g % 8 for g in grids)
+    assert [2 * g % 8 for g in grids] == [4, 0, 6, 6, 4]
+    assert {E // H for B, T, E, H in eo.LONG_TAIL_SHAPES} == {4, 8, 16, 32, 64}
+    c = eo.long_attn_case(2, 129, 16, 2, 0.0, "left", False, "randn", 7)
+    assert bool((c.ids == 0).any()) and bool((c.ids == 7).any())
+    assert bool(c.valid[c.ids == 0].all()) and not bool(c.valid[c.ids == 7].any())
+
+
+@pytest.mark.parametrize("case", [c for c in eo.LONG_HARD_CASES if not c[6]], ids=str)
+def test_long_family_conditions(case):
+    """max |score| in [20, 80]; the per-tile maximum climbs (falls) from each
+    64-key tile to the next (family_ok has the partial last tile of "rising")"""
+    c = eo.long_attn_case(*case)
+    print(f"{case} walk={c.walk} smax={c.smax:.1f} last={c.last:.3f} tiles="
+          + " ".join(f"{t:.1f}" for t in c.tiles))
+    assert eo.family_ok(c.family, c.T, c.smax, c.tiles, c.last)
+    lo, hi = eo.LONG_SCORE_RANGE
+    assert lo == 20.0 and hi == 80.0 and lo <= c.smax <= hi
+    full = c.tiles[: c.T // 64]
+    if c.family == "rising":
+        assert all(b > a for a, b in zip(full, full[1:])) and (c.T % 64 == 0 or c.last >= 1 / 16)
+    if c.family == "falling":
+        assert all(b < a for a, b in zip(c.tiles, c.tiles[1:]))
+    # the same inputs whatever the mask: the causal case shares them
+    assert torch.equal(c.qkv, eo.long_attn_case(*case[:6], True, *case[7:]).qkv)
+
+
+@pytest.mark.parametrize("case", eo.LONG_CASES, ids=str)
+def test_reference_error_long_attention(case):
+    """the yardstick of every tiled-attention case is finite and never 0, and
+    the fp32 reference itself meets the uniform-row rule of lse"""
+    c = eo.long_attn_case(*case)
+    got = eo.ref_run(c)
+    e = eo.errs(got, c.exact)
+    _show(f"fp32 reference {case}", e)
+    assert set(e) == {"out", "dqkv", "lse"}
+    assert all(math.isfinite(v) and 0 < v < 1e-3 for v in e.values()), e
+    eo.check_uniform_lse(got["lse"], c.exact["lse"])
+
+
+def test_planted_lse_errors():
+    c = eo.long_attn_case(2, 129, 16, 2, 0.0, "left", True, "randn")
+    got = _clean(c)
+    eo.check_uniform_lse(got["lse"], c.exact["lse"])
+    uni = c.exact["lse"] < eo.LSE_UNIFORM
+    assert bool(uni.any()) and not bool(uni.all())
+    # an ordinary row off by 1e-4 relative: caught although uniform rows sit at -1e9
+    bad = {k: v.clone() for k, v in got.items()}
+    i = tuple(int(v[0]) for v in torch.nonzero(~uni, as_tuple=True))
+    bad["lse"][i] += 1e-4 * max(1.0, abs(float(c.exact["lse"][i])))
+    assert _rejected(bad, c, ["lse"])
+    assert eo.row_err(bad["lse"], c.exact["lse"], "elem") < 1e-8     # ("elem" would pass it)
+    # a uniform row a whole ulp off, and one that the backward would not recognise
+    for v in (-1e9 + 128.0, -4e8):
+        bad = {k: t.clone() for k, t in got.items()}
+        bad["lse"][tuple(int(t[0]) for t in torch.nonzero(uni, as_tuple=True))] = v
+        assert not _rejected(bad, c, ["lse"])
+        with pytest.raises(AssertionError):
+            eo.check_uniform_lse(bad["lse"], c.exact["lse"])
+        with pytest.raises(AssertionError):
+            eo.assert_within(bad, c, "planted")
+    # a skipped rescale of the running sum: the early tiles' share of l kept at the old maximum
+    r = eo.long_attn_case(2, 129, 16, 2, 0.0, "none", False, "rising")
+    bad = _clean(r)
+    bad["lse"] += 1e-3
+    assert _rejected(bad, r, ["lse"])
 
 
 # ------------------------------------------------------------- LDS formula
