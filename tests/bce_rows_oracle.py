@@ -23,6 +23,7 @@ import functools
 
 import torch
 
+from tests import xent_oracle as xo
 from tests.xent_oracle import BOUND, rel_err  # noqa: F401  (shared with the tests)
 
 WIDTHS = (16, 32, 64, 128, 256)
@@ -34,6 +35,14 @@ SHAPES = [(7, 1), (7, 7), (65, 64), (65, 65), (64, 127), (320, 129), (320, 513),
 # (N, S, V, hs): the shapes above, one with saturating scores, one at a larger V
 CASES = [(N, S, V, 1.0) for N, S in SHAPES] + [(320, 513, V, 12.0), (65, 65, 70001, 1.0)]
 NAMES = ("dH", "loss", "dW", "db", "mean")
+# chosen numbers of valid tokens, and lengths of the hot label's run (one wave
+# walks a run 64 tokens at a time), at NV_SHAPE
+NV = (1, 63, 64, 65, 129)
+HOT = (63, 64, 65)
+HOT_NV = 129
+NV_SHAPE = (200, 129)       # (N, S)
+NV_TWICE = (97, 257)        # two calls bit-identical, at (NV_TWICE_N, 129)
+NV_TWICE_N = 264
 
 
 def valid_negs(negs: torch.Tensor, V: int) -> torch.Tensor:
@@ -51,15 +60,17 @@ def label_order(labels: torch.Tensor, V: int, ignore: int = IGNORE) -> torch.Ten
 
 
 @functools.lru_cache(maxsize=None)
-def make_case(N: int, S: int, E: int, V: int = V, hs: float = 1.0):
+def make_case(N: int, S: int, E: int, V: int = V, hs: float = 1.0, nv=None, hot=None):
     """CPU inputs (H, W, b, labels, order, negs). The valid negatives are
     distinct and ascending, rows 0 and V - 1 among them (S >= 2); about 30 % of
     the slots are holes (-1, V or V + 5), the first and the last slot among them
     (S >= 3). The first third of the tokens shares one label that is no
     negative (a quarter of them ignored); of the others about three quarters
     are ignored (0, -3, V or V + 7), which makes about 60 % in all, and a quarter
-    of the rest have a label that is one of the negatives. Cached: treat as
-    read-only."""
+    of the rest have a label that is one of the negatives. With ``nv`` exactly
+    that many tokens are valid, spread evenly over the N; ``hot`` of them (a
+    third by default) share the one label that is no negative, the last two
+    share a label that is a negative. Cached: treat as read-only."""
     g = torch.Generator().manual_seed(7919 * E + 31 * N + S + V)
     H = torch.randn(N, E, generator=g) * hs
     W = torch.randn(V, E, generator=g) * 0.2
@@ -93,8 +104,22 @@ def make_case(N: int, S: int, E: int, V: int = V, hs: float = 1.0):
     labels[N - 1] = hits[-1] if hits.numel() else spare[1]
     if N > 4:
         labels[N - 2] = labels[N - 1]                          # a short run on the add path
-    if N >= 320:
+    if N >= 320 and nv is None:
         assert int((labels == spare[0]).sum()) > 64
+    if nv is not None:
+        pos = xo.valid_positions(N, nv, "spread")
+        lab = spare[1 + torch.randint(0, spare.numel() - 1, (nv,), generator=g)]
+        if hits.numel():
+            hit = torch.rand(nv, generator=g) < 0.25
+            lab = torch.where(hit, hits[torch.randint(0, hits.numel(), (nv,), generator=g)], lab)
+        run = nv // 3 if hot is None else hot
+        assert run <= nv
+        lab[:run] = spare[0]
+        if nv - run >= 2:
+            lab[nv - 2:] = hits[-1] if hits.numel() else spare[1]
+        labels = torch.tensor([IGNORE, -3, V, V + 7])[torch.randint(0, 4, (N,), generator=g)]
+        labels[pos] = lab
+        assert int((labels == spare[0]).sum()) == run
     return H, W, b, labels, label_order(labels, V), negs
 
 
@@ -108,8 +133,10 @@ def _sigmoid(z):
 
 
 def oracle(H, W, b, labels, negs, beta=1.0, ignore=IGNORE):
-    """-> (dH, lossv, dW [V, E], db [V], mean loss), float64; dW / db are zero
-    outside the rows named by valid negatives and valid labels."""
+    """-> (dH, lossv, dW [V, E], db [V], mean loss, db_terms [V]), float64;
+    dW / db are zero outside the rows named by valid negatives and valid
+    labels. db_terms is the magnitude of the terms db sums: a row that is a
+    negative and a label sums terms of both signs (xent_oracle.db_err)."""
     H, W, b = H.double(), W.double(), b.double()
     V = W.shape[0]
     rows = valid_negs(negs, V)
@@ -129,13 +156,17 @@ def oracle(H, W, b, labels, negs, beta=1.0, ignore=IGNORE):
     db[rows] = dz.sum(0)
     dW.index_add_(0, y, dzy[:, None] * H)
     db.index_add_(0, y, dzy)
-    return dz @ W[rows] + dzy[:, None] * W[y], lossv, dW, db, lossv.sum() / nv
+    terms = torch.zeros_like(b)
+    terms[rows] = dz.sum(0)
+    terms.index_add_(0, y, -dzy)
+    return dz @ W[rows] + dzy[:, None] * W[y], lossv, dW, db, lossv.sum() / nv, terms
 
 
 @functools.lru_cache(maxsize=None)
-def oracle_case(N: int, S: int, E: int, V: int = V, hs: float = 1.0, beta: float = 1.0):
+def oracle_case(N: int, S: int, E: int, V: int = V, hs: float = 1.0, beta: float = 1.0,
+                nv=None, hot=None):
     """Cached: treat as read-only."""
-    H, W, b, labels, _, negs = make_case(N, S, E, V, hs)
+    H, W, b, labels, _, negs = make_case(N, S, E, V, hs, nv, hot)
     return oracle(H, W, b, labels, negs, beta)
 
 
@@ -147,6 +178,41 @@ def named_rows(labels, negs, V, ignore=IGNORE) -> torch.Tensor:
         m[valid_negs(negs, V)] = True
         m[labels[valid]] = True
     return m
+
+
+def on_named(out, named):
+    """[dH, lossv, dW, db, mean] -> {name: tensor}, dW / db on the named rows"""
+    d = dict(zip(NAMES, [out[0], out[1], out[2].cpu()[named], out[3].cpu()[named], out[4]]))
+    if len(out) > 5:
+        d["db_terms"] = out[5][named]
+    return d
+
+
+@functools.lru_cache(maxsize=None)
+def ref_err(N: int, S: int, E: int, V: int = V, hs: float = 1.0, beta: float = 1.0, nv=None,
+            hot=None):
+    """{name: row_err of ``ops.reference.linear_bce_rows`` in float32 on the
+    CPU against the oracle}: the yardstick of the per-row bound, once per
+    case. dW / db are compared on the named rows only."""
+    from tdfo_amd.ops import reference as ref
+
+    H, W, b, labels, _, negs = make_case(N, S, E, V, hs, nv, hot)
+    out = [torch.zeros_like(H), torch.zeros(N), torch.zeros_like(W), torch.zeros_like(b)]
+    k = ref.linear_bce_rows(H, W, b, labels, negs, beta, IGNORE, *out)
+    assert k == int(valid_tokens(labels, V).sum())
+    named = named_rows(labels, negs, V)
+    want = oracle_case(N, S, E, V, hs, beta, nv, hot)
+    return xo.errs(on_named(out + [out[1].sum() / max(1, k)], named), on_named(want, named))
+
+
+def assert_within(out, args, tag):
+    """The kernel's [dH, lossv, dW, db, mean] on the case ``args`` = (N, S, E,
+    V, hs, beta, nv, hot) within the per-row bound of tests/xent_oracle.py"""
+    N, S, E, Vv, hs, beta, nv, hot = args
+    _, _, _, labels, _, negs = make_case(N, S, E, Vv, hs, nv, hot)
+    named = named_rows(labels, negs, Vv)
+    xo.assert_bound(xo.errs(on_named(out, named), on_named(oracle_case(*args), named)),
+                    ref_err(*args), tag)
 
 
 def candidate_case(N: int = 1030, S: int = 512, n_items: int = 3000, seed: int = 3):

@@ -174,3 +174,46 @@ def test_bce_trainer_learns():
         if i % 10 == 9:
             losses.append(tr.pop_loss())
     assert losses[-1] < losses[0], losses
+
+
+# ------------------------------------------------ chosen numbers of valid tokens
+@pytest.mark.parametrize("E", (16, 256))
+def test_nv_builder_and_yardstick(E):
+    """``make_case(nv=, hot=)`` yields exactly nv valid tokens and a hot run
+    of the asked length, and the fp32 reference has a finite, non-zero row_err
+    on every such case."""
+    N, S = bo.NV_SHAPE
+    todo = [(N, nv, None) for nv in bo.NV] + [(N, bo.HOT_NV, h) for h in bo.HOT]
+    todo += [(bo.NV_TWICE_N, nv, None) for nv in bo.NV_TWICE]
+    for n, nv, hot in todo:
+        labels = bo.make_case(n, S, E, bo.V, 1.0, nv, hot)[3]
+        on = bo.valid_tokens(labels, bo.V)
+        assert int(on.sum()) == nv
+        run = int(torch.bincount(labels[on]).max())
+        assert run == (hot if hot is not None else max(1, nv // 3)) or nv < 3
+        if n == N:
+            for k, v in bo.ref_err(n, S, E, bo.V, 1.0, 0.3, nv, hot).items():
+                assert 0 < v < 1e-2, (nv, hot, k, v)
+
+
+@pytest.mark.parametrize("N,S,E,nv,beta", [(9, 5, 16, 4, 1.0), (40, 33, 64, 17, 0.3),
+                                           (20, 129, 128, 20, 0.3)])
+def test_bce_oracle_matches_autograd_fp64(N, S, E, nv, beta):
+    V = 300
+    H, W, b, labels, _, negs = bo.make_case(N, S, E, V, 1.0, nv)
+    want = bo.oracle(H, W, b, labels, negs, beta)
+    rows = bo.valid_negs(negs, V)
+    on = bo.valid_tokens(labels, V)
+    assert int(on.sum()) == nv
+    Hd, Wd, bd = (t.double().requires_grad_(True) for t in (H, W, b))
+    y = labels[on]
+    z = Hd[on] @ Wd[rows].t() + bd[rows]
+    zy = (Hd[on] * Wd[y]).sum(1) + bd[y]
+    keep = (rows.view(1, -1) != y.view(-1, 1)).double()
+    per = (beta * F.softplus(-zy) + (F.softplus(z) * keep).sum(1)) / (keep.sum(1) + 1)
+    m = per.sum() / nv
+    m.backward()
+    lossv = torch.zeros(N, dtype=torch.float64)
+    lossv[on] = per.detach()
+    for k, a, r in zip(bo.NAMES, want, (Hd.grad, lossv, Wd.grad, bd.grad, m.detach())):
+        assert bo.rel_err(a, r) < 1e-12, k

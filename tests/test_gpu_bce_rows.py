@@ -250,3 +250,45 @@ def test_candidate_builder():
     torch.cuda.synchronize()
     assert torch.equal(got[0].cpu(), want[0]) and torch.equal(got[1].cpu(), want[1])
     bo.check_candidates(labels, neg, got[0], got[1], 3002)
+
+
+# --------------------------------------------- per row, at chosen valid counts
+def _per_row(args, tag):
+    N, S, E, V, hs, beta, nv, hot = args
+    case = bo.make_case(N, S, E, V, hs, nv, hot)
+    out = _run(*case, beta=beta)
+    named = bo.named_rows(case[3], case[5], V)
+    assert bool((out[2].cpu()[~named] == FILL).all()) and bool((out[3].cpu()[~named] == FILL).all())
+    bo.assert_within(out[:4] + [out[4][0]], args, tag)
+    ign = ~bo.valid_tokens(case[3], V)
+    assert int((~ign).sum()) == nv
+    assert float(out[0].cpu()[ign].abs().sum()) == 0 and float(out[1].cpu()[ign].abs().sum()) == 0
+
+
+@pytest.mark.parametrize("E", bo.WIDTHS)
+@pytest.mark.parametrize("nv", bo.NV)
+def test_chosen_nv_per_row(nv, E):
+    """Exactly nv valid tokens: dH and dW per row, lossv and db per element
+    and the mean within max(8 x row_err(fp32 reference), 2^-20) of fp64, for
+    beta 1.0 and 0.3; unnamed rows keep their fill; ignored tokens get exact
+    zeros."""
+    N, S = bo.NV_SHAPE
+    for beta in bo.BETAS:
+        _per_row((N, S, E, bo.V, 1.0, beta, nv, None), f"BCE E={E} N={N} S={S} nv={nv} beta={beta}")
+
+
+@pytest.mark.parametrize("E", bo.WIDTHS)
+@pytest.mark.parametrize("hot", bo.HOT)
+def test_hot_run_at_wave_edge(hot, E):
+    """The hot label's run is walked by one wave, 64 tokens at a time: runs of
+    63, 64 and 65 tokens."""
+    N, S = bo.NV_SHAPE
+    _per_row((N, S, E, bo.V, 1.0, 0.3, bo.HOT_NV, hot), f"BCE hot run {hot} E={E}")
+
+
+@pytest.mark.parametrize("E", bo.WIDTHS)
+@pytest.mark.parametrize("nv", bo.NV_TWICE)
+def test_chosen_nv_bit_identical(nv, E):
+    case = bo.make_case(bo.NV_TWICE_N, bo.NV_SHAPE[1], E, bo.V, 1.0, nv)
+    for x, z in zip(_run(*case, beta=0.3), _run(*case, beta=0.3)):
+        assert torch.equal(x, z)

@@ -165,3 +165,42 @@ def test_full_loss_is_todays_trainer():
             t.step()
     assert torch.equal(a.opt.flat, b.opt.flat) and torch.equal(a.item.weight, b.item.weight)
     assert not hasattr(b, "cand")
+
+
+# ------------------------------------------------ chosen numbers of valid tokens
+@pytest.mark.parametrize("E", (16, 256))
+def test_nv_builder_and_yardstick(E):
+    """``make_case(nv=)`` yields exactly nv valid tokens, and the fp32
+    reference has a finite, non-zero row_err on every such case."""
+    N, M = xr.NV_SHAPE
+    for n, nvs in ((N, xr.NV), (xr.NV_TWICE_N, xr.NV_TWICE)):
+        for nv in nvs:
+            H, W, b, cand, target, _ = xr.make_case(n, M, E, xr.V, 1.0, False, nv)
+            assert xr.n_valid(cand, target, xr.V) == nv
+            assert int((xr.oracle_case(n, M, E, xr.V, 1.0, False, nv)[1] != 0).sum()) == nv
+            if n == N:
+                for k, v in xr.ref_err(n, M, E, xr.V, 1.0, False, nv).items():
+                    assert 0 < v < 1e-2, (nv, k, v)
+    # the cases without nv are the ones they were
+    assert xr.n_valid(*xr.make_case(320, 129, E)[3:5], xr.V) not in (0, 320)
+
+
+@pytest.mark.parametrize("N,M,E,nv,wc", [(9, 5, 16, 4, False), (40, 33, 64, 17, True),
+                                         (20, 129, 128, 20, False)])
+def test_rows_oracle_matches_autograd_fp64(N, M, E, nv, wc):
+    V = 300
+    H, W, b, cand, target, corr = xr.make_case(N, M, E, V, 1.0, wc, nv)
+    want = xr.oracle(H, W, b, cand, target, corr)
+    slots = xr.valid_slots(cand, V)
+    c2, t2, k2 = xr.without_holes(cand, target, V, corr)
+    Hd, Wd, bd = (t.double().requires_grad_(True) for t in (H, W, b))
+    z = Hd @ Wd[c2].t() + bd[c2]
+    if k2 is not None:
+        z = z + k2.double()
+    y = torch.where(t2 >= 0, t2, torch.full_like(t2, -100))
+    per = F.cross_entropy(z, y, ignore_index=-100, label_smoothing=xr.EPS, reduction="none")
+    assert int((y >= 0).sum()) == nv and slots.numel() == c2.numel()
+    m = per.sum() / nv
+    m.backward()
+    for k, a, r in zip(xr.NAMES, want, (Hd.grad, per.detach(), Wd.grad, bd.grad, m.detach())):
+        assert xr.rel_err(a, r) < 1e-12, k

@@ -18,6 +18,7 @@ import functools
 
 import torch
 
+from tests import xent_oracle as xo
 from tests.xent_oracle import BOUND, EPS, rel_err  # noqa: F401  (shared with the tests)
 
 WIDTHS = (16, 32, 64, 128, 256)
@@ -25,6 +26,11 @@ V = 5003
 # (N, M): the own tile (64) and the streamed tiles (128 / 64 / 32 rows) at their edges
 SHAPES = [(7, 1), (7, 7), (65, 64), (65, 65), (64, 127), (320, 129), (320, 513), (1030, 2049)]
 NAMES = ("dH", "loss", "dW", "db", "mean")
+# chosen numbers of valid tokens (the 64-token own tile at its edges), at NV_SHAPE
+NV = (1, 63, 64, 65, 129)
+NV_SHAPE = (200, 129)       # (N, M)
+NV_TWICE = (97, 257)        # two calls bit-identical, at (NV_TWICE_N, 129)
+NV_TWICE_N = 264
 
 
 def valid_slots(cand: torch.Tensor, V: int) -> torch.Tensor:
@@ -32,12 +38,15 @@ def valid_slots(cand: torch.Tensor, V: int) -> torch.Tensor:
 
 
 @functools.lru_cache(maxsize=None)
-def make_case(N: int, M: int, E: int, V: int = V, hs: float = 1.0, with_corr: bool = False):
+def make_case(N: int, M: int, E: int, V: int = V, hs: float = 1.0, with_corr: bool = False,
+              nv=None):
     """CPU inputs (H, W, b, cand, target, corr). About 30 % of the candidate
     slots are holes (-1, V or V + 5), the first and the last slot among them
     (M >= 3); rows 0 and V - 1 are candidates; about 60 % of the tokens are
     ignored (-1, M, M + 3 or a slot that is a hole); several tokens share one
-    positive. Cached: treat as read-only."""
+    positive. With ``nv`` exactly that many tokens are valid, spread evenly over
+    the N, the first on the first and the last on the last valid candidate, a
+    third of them on one shared positive. Cached: treat as read-only."""
     g = torch.Generator().manual_seed(7919 * E + 31 * N + M + V)
     H = torch.randn(N, E, generator=g) * hs
     W = torch.randn(V, E, generator=g) * 0.2
@@ -65,12 +74,23 @@ def make_case(N: int, M: int, E: int, V: int = V, hs: float = 1.0, with_corr: bo
     if N > 4:
         target[2] = target[3] = ok[ok.numel() // 2]
     corr = torch.randn(M, generator=g) * 0.5 if with_corr else None
+    if nv is not None:
+        pos = xo.valid_positions(N, nv, "spread")
+        lab = ok[torch.randint(0, ok.numel(), (nv,), generator=g)]
+        lab[: nv // 3] = ok[ok.numel() // 2]
+        if nv >= 1:
+            lab[0] = ok[0]
+        if nv >= 2:
+            lab[nv - 1] = ok[-1]
+        target = torch.tensor([-1, M, M + 3])[torch.randint(0, 3, (N,), generator=g)]
+        target[pos] = lab
     return H, W, b, cand, target, corr
 
 
 def oracle(H, W, b, cand, target, corr=None, eps=EPS):
-    """-> (dH, lossv, dW [V, E], db [V], mean loss), float64; dW / db are zero
-    outside the rows named by valid candidates."""
+    """-> (dH, lossv, dW [V, E], db [V], mean loss, db_terms [V]), float64;
+    dW / db are zero outside the rows named by valid candidates. db_terms is
+    the magnitude of the terms db sums (xent_oracle.db_err)."""
     H, W, b = H.double(), W.double(), b.double()
     N, V, M = H.shape[0], W.shape[0], cand.numel()
     slots = valid_slots(cand, V)
@@ -85,7 +105,7 @@ def oracle(H, W, b, cand, target, corr=None, eps=EPS):
     dW, db = torch.zeros_like(W), torch.zeros_like(b)
     if Mv == 0:
         zero = torch.zeros((), dtype=torch.float64)
-        return torch.zeros_like(H), zero.expand(N).clone(), dW, db, zero
+        return torch.zeros_like(H), zero.expand(N).clone(), dW, db, zero, torch.zeros_like(b)
     z = H @ W[rows].t() + b[rows]
     if corr is not None:
         z = z + corr.double()[slots]
@@ -98,14 +118,66 @@ def oracle(H, W, b, cand, target, corr=None, eps=EPS):
     dz = dz * valid[:, None] / nv
     dW[rows] = dz.t() @ H
     db[rows] = dz.sum(0)
-    return dz @ W[rows], lossv, dW, db, lossv.sum() / nv
+    terms = torch.zeros_like(b)
+    terms[rows] = 2 * (torch.exp(z - lse[:, None]) * valid[:, None]).sum(0) / nv - db[rows]
+    return dz @ W[rows], lossv, dW, db, lossv.sum() / nv, terms
 
 
 @functools.lru_cache(maxsize=None)
-def oracle_case(N: int, M: int, E: int, V: int = V, hs: float = 1.0, with_corr: bool = False):
+def oracle_case(N: int, M: int, E: int, V: int = V, hs: float = 1.0, with_corr: bool = False,
+                nv=None):
     """Cached: treat as read-only."""
-    H, W, b, cand, target, corr = make_case(N, M, E, V, hs, with_corr)
+    H, W, b, cand, target, corr = make_case(N, M, E, V, hs, with_corr, nv)
     return oracle(H, W, b, cand, target, corr)
+
+
+def n_valid(cand, target, V: int) -> int:
+    M = cand.numel()
+    inr = (target >= 0) & (target < M)
+    c = cand[target.clamp(0, M - 1)]
+    return int((inr & (c >= 0) & (c < V)).sum())
+
+
+def named_rows(cand, V: int) -> torch.Tensor:
+    """bool [V]: the rows of dW / db a call assigns"""
+    m = torch.zeros(V, dtype=torch.bool)
+    m[cand[valid_slots(cand, V)]] = True
+    return m
+
+
+def on_named(out, named):
+    """[dH, lossv, dW, db, mean] -> {name: tensor}, dW / db on the named rows"""
+    d = dict(zip(NAMES, [out[0], out[1], out[2].cpu()[named], out[3].cpu()[named], out[4]]))
+    if len(out) > 5:
+        d["db_terms"] = out[5][named]
+    return d
+
+
+@functools.lru_cache(maxsize=None)
+def ref_err(N: int, M: int, E: int, V: int = V, hs: float = 1.0, with_corr: bool = False,
+            nv=None):
+    """{name: row_err of ``ops.reference.linear_xent_rows`` in float32 on the
+    CPU against the oracle}: the yardstick of the per-row bound, once per
+    case. dW / db are compared on the named rows only."""
+    from tdfo_amd.ops import reference as ref
+
+    H, W, b, cand, target, corr = make_case(N, M, E, V, hs, with_corr, nv)
+    out = [torch.zeros_like(H), torch.zeros(N), torch.zeros_like(W), torch.zeros_like(b)]
+    k = ref.linear_xent_rows(H, W, b, cand, target, EPS, *out, corr=corr)
+    assert k == n_valid(cand, target, V)
+    named = named_rows(cand, V)
+    want = oracle_case(N, M, E, V, hs, with_corr, nv)
+    return xo.errs(on_named(out + [out[1].sum() / max(1, k)], named), on_named(want, named))
+
+
+def assert_within(out, args, tag):
+    """The kernel's [dH, lossv, dW, db, mean] on ``make_case(*args)`` within
+    the per-row bound of tests/xent_oracle.py"""
+    cand = make_case(*args)[3]
+    Vv = args[3] if len(args) > 3 else V
+    named = named_rows(cand, Vv)
+    xo.assert_bound(xo.errs(on_named(out, named), on_named(oracle_case(*args), named)),
+                    ref_err(*args), tag)
 
 
 def without_holes(cand, target, V, corr=None):
