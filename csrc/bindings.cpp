@@ -224,7 +224,8 @@ void interaction_bwd(const Tensor& dz, const Tensor& dense, const Tensor& emb,
 
 // ------------------------------------------------------------ attention
 tdfo::AttnArgs attn_args(const Tensor& qkv, const Tensor& ids, int64_t H, double rate,
-                         int64_t seed, const c10::optional<Tensor>& step, int64_t pad_id) {
+                         int64_t seed, const c10::optional<Tensor>& step, int64_t pad_id,
+                         bool stream = false) {
   check_dev(qkv, "qkv"); check_dev(ids, "ids");
   TORCH_CHECK(qkv.scalar_type() == at::kFloat && qkv.is_contiguous() && qkv.dim() == 3,
               "attention: qkv fp32 contiguous [B, T, 3E]");
@@ -232,8 +233,13 @@ tdfo::AttnArgs attn_args(const Tensor& qkv, const Tensor& ids, int64_t H, double
               ids.size(0) == qkv.size(0) && ids.size(1) == qkv.size(1), "attention: ids int64 [B, T]");
   const int64_t E3 = qkv.size(2);
   TORCH_CHECK(E3 % 3 == 0 && H > 0 && (E3 / 3) % H == 0, "attention: 3E must split into H heads");
-  TORCH_CHECK(qkv.size(1) <= tdfo::ATTN_LONG_MAXT,
-              "attention: T <= 512 (one-wave kernel up to 64, tiled kernel with lse above)");
+  if (stream) {
+    TORCH_CHECK(qkv.size(1) > tdfo::ATTN_SHORT_MAXT && qkv.size(1) <= tdfo::ATTN_STREAM_MAXT,
+                "attention (streaming): 64 < T <= 4096");
+  } else {
+    TORCH_CHECK(qkv.size(1) <= tdfo::ATTN_LONG_MAXT,
+                "attention: T <= 512 (one-wave kernel up to 64, tiled kernel with lse above)");
+  }
   TORCH_CHECK(rate >= 0.0 && rate < 1.0, "attention: dropout rate in [0, 1)");
   tdfo::AttnArgs a{};
   a.qkv = qkv.data_ptr<float>(); a.ids = ids.data_ptr<int64_t>();
@@ -291,6 +297,39 @@ void attention_bwd(const Tensor& qkv, const Tensor& ids, const Tensor& dout, int
               dqkv.numel() == qkv.numel(), "attention: dqkv fp32 [B, T, 3E]");
   a.dout = dout.data_ptr<float>(); a.dqkv = dqkv.data_ptr<float>();
   tdfo::attention_bwd(a, cur_stream());
+}
+
+// the streaming kernels (64 < T <= 4096): workspaces are required arguments
+float* attn_f32_ws(const Tensor& t, int64_t numel, const char* what) {
+  check_dev(t, what);
+  TORCH_CHECK(t.scalar_type() == at::kFloat && t.is_contiguous() && t.numel() == numel,
+              "attention (streaming): ", what, " must be fp32 contiguous with ", numel,
+              " elements");
+  return t.data_ptr<float>();
+}
+
+void attention_stream_fwd(const Tensor& qkv, const Tensor& ids, int64_t H, double rate,
+                          int64_t seed, const c10::optional<Tensor>& step, int64_t pad_id,
+                          const Tensor& out, const Tensor& lse, bool causal) {
+  auto a = attn_args(qkv, ids, H, rate, seed, step, pad_id, true);
+  a.causal = causal ? 1 : 0;
+  a.out = attn_f32_ws(out, qkv.numel() / 3, "out [B, T, E]");
+  a.lse = attn_f32_ws(lse, (int64_t)a.B * a.H * a.T, "lse [B, H, T]");
+  tdfo::attention_stream_fwd(a, cur_stream());
+}
+
+void attention_stream_bwd(const Tensor& qkv, const Tensor& ids, const Tensor& dout, int64_t H,
+                          double rate, int64_t seed, const c10::optional<Tensor>& step,
+                          int64_t pad_id, const Tensor& dqkv, const Tensor& out, const Tensor& lse,
+                          const Tensor& delta, bool causal) {
+  auto a = attn_args(qkv, ids, H, rate, seed, step, pad_id, true);
+  a.causal = causal ? 1 : 0;
+  a.out = attn_f32_ws(out, qkv.numel() / 3, "out [B, T, E]");
+  a.lse = attn_f32_ws(lse, (int64_t)a.B * a.H * a.T, "lse [B, H, T]");
+  a.delta = attn_f32_ws(delta, (int64_t)a.B * a.H * a.T, "delta [B, H, T]");
+  a.dout = attn_f32_ws(dout, qkv.numel() / 3, "dout [B, T, E]");
+  a.dqkv = attn_f32_ws(dqkv, qkv.numel(), "dqkv [B, T, 3E]");
+  tdfo::attention_stream_bwd(a, cur_stream());
 }
 
 void check_f32c(const Tensor& t, const char* name);
@@ -2063,6 +2102,11 @@ TORCH_LIBRARY(tdfo, m) {
         "Tensor(a!) out, Tensor(b!)? lse=None, bool causal=False) -> ()");
   m.def("attention_bwd(Tensor qkv, Tensor ids, Tensor dout, int H, float rate, int seed, Tensor? step, "
         "int pad_id, Tensor(a!) dqkv, Tensor? out=None, Tensor? lse=None, bool causal=False) -> ()");
+  m.def("attention_stream_fwd(Tensor qkv, Tensor ids, int H, float rate, int seed, Tensor? step, "
+        "int pad_id, Tensor(a!) out, Tensor(b!) lse, bool causal=False) -> ()");
+  m.def("attention_stream_bwd(Tensor qkv, Tensor ids, Tensor dout, int H, float rate, int seed, "
+        "Tensor? step, int pad_id, Tensor(a!) dqkv, Tensor out, Tensor lse, Tensor(b!) delta, "
+        "bool causal=False) -> ()");
   m.def("layernorm_fwd(Tensor x, int n, float eps, Tensor gamma, Tensor beta, Tensor(a!) y, "
         "Tensor(b!) mean, Tensor(c!) rstd) -> ()");
   m.def("layernorm_bwd(Tensor x, Tensor g, int n, Tensor gamma, Tensor mean, Tensor rstd, "
@@ -2190,6 +2234,8 @@ TORCH_LIBRARY_IMPL(tdfo, CUDA, m) {
   m.impl("encoder_layer_fwd", encoder_layer_fwd);
   m.impl("encoder_layer_bwd", encoder_layer_bwd);
   m.impl("attention_bwd", attention_bwd);
+  m.impl("attention_stream_fwd", attention_stream_fwd);
+  m.impl("attention_stream_bwd", attention_stream_bwd);
   m.impl("layernorm_fwd", layernorm_fwd);
   m.impl("layernorm_bwd", layernorm_bwd);
   m.impl("seq_prologue_fwd", seq_prologue_fwd);

@@ -574,6 +574,7 @@ struct AttnArgs {
   // The dropout hash keeps its keys, so the mask is the non-causal one
   // restricted to j <= i.
   int causal = 0;
+  float* delta = nullptr;      // [B,H,T] D_i = dO_i . O_i, streaming backward only (workspace)
 };
 // T <= 64: attention.hip (one wave per (sample, head)); 64 < T <= 512: the
 // tiled kernels below, which also need lse (and, backward, the forward's out).
@@ -586,6 +587,13 @@ constexpr int ATTN_SHORT_MAXT = 64;
 constexpr int ATTN_LONG_MAXT = 512;
 void attention_long_fwd(const AttnArgs& a, hipStream_t s);
 void attention_long_bwd(const AttnArgs& a, hipStream_t s);
+// Streaming core (attention_stream.hip), 64 < T <= 4096: the same tiles, but a
+// block's LDS and set-up do not depend on T (per-row data travels with its
+// tile; D = dO . O comes from a pre-pass into AttnArgs::delta). The hash keys a
+// row by (b*H+h)*4096 + i above T = 512 and by (b*H+h)*512 + i up to it.
+constexpr int ATTN_STREAM_MAXT = 4096;
+void attention_stream_fwd(const AttnArgs& a, hipStream_t s);
+void attention_stream_bwd(const AttnArgs& a, hipStream_t s);
 
 // --------------------------------------------------- encoder layer ----
 // Fused Bert4Rec transformer block (encoder.hip), fp32, one workgroup per

@@ -6,7 +6,11 @@ repeats, median / min / max), their ratio, the largest difference of outputs
 and gradients, and the HIP time's share of the f32-MFMA time of its algorithmic
 FLOPs (4 B H T^2 d_k forward + 10 B H T^2 d_k backward) at 155 TF.
 --causal times the causal kernels (keys j <= i) against eager torch with the
-same combined mask; the FLOPs then count the T (T + 1) / 2 visible pairs."""
+same combined mask; the FLOPs then count the T (T + 1) / 2 visible pairs.
+--stream routes every shape with T > 64 through ops.attention_stream_fwd / bwd
+(attention_stream.hip; T > 512 always takes them) and, at T <= 512, times the
+attention_long.hip family next to it in the same alternation ("long_ms",
+"stream_over_long")."""
 import argparse
 import json
 import math
@@ -29,6 +33,8 @@ ap.add_argument("--iters", type=int, default=20, help="calls per timed window")
 ap.add_argument("--repeats", type=int, default=7)
 ap.add_argument("--no-torch", action="store_true")
 ap.add_argument("--causal", action="store_true", help="causal attention (keys j <= i)")
+ap.add_argument("--stream", action="store_true",
+                help="time the streaming kernels at every T > 64 (T > 512 always does)")
 args = ap.parse_args()
 assert torch.cuda.is_available(), "bench_attention needs a GPU"
 dev = "cuda"
@@ -59,10 +65,20 @@ for spec in args.shapes.split(","):
     ckw = {"causal": True} if args.causal else {}
     future = torch.ones(T, T, dtype=torch.bool, device=dev).triu(1)
 
-    def hip():
+    stream = T > ops.ATTN_LONG_MAXT or (args.stream and T > ops.ATTN_SHORT_MAXT)
+    delta = torch.empty(B, H, T, device=dev) if stream else None
+
+    def long():
         ops.attention_fwd(qkv, ids, H, args.rate, 1, step, 0, out, lse=lse, **ckw)
         ops.attention_bwd(qkv, ids, dout, H, args.rate, 1, step, 0, dqkv, out=out, lse=lse,
                           **ckw)
+
+    def streaming():
+        ops.attention_stream_fwd(qkv, ids, H, args.rate, 1, step, 0, out, lse, **ckw)
+        ops.attention_stream_bwd(qkv, ids, dout, H, args.rate, 1, step, 0, dqkv, out, lse, delta,
+                                 **ckw)
+
+    hip = streaming if stream else long
 
     x = qkv.clone().requires_grad_(True)
     mask = (ids != 0).view(B, 1, 1, T)
@@ -79,7 +95,11 @@ for spec in args.shapes.split(","):
         o.backward(dout)
         res["o"] = o
 
-    fns = {"hip": hip} if args.no_torch else {"hip": hip, "eager": eager}
+    fns = {"hip": hip}
+    if stream and T <= ops.ATTN_LONG_MAXT:
+        fns["long"] = long
+    if not args.no_torch:
+        fns["eager"] = eager
     for fn in fns.values():                      # warm-up: code objects, library algorithms
         for _ in range(5):
             fn()
@@ -88,13 +108,16 @@ for spec in args.shapes.split(","):
     for _ in range(args.repeats):                # alternate the two in one process
         for k, fn in fns.items():
             ms[k].append(window(fn, args.iters))
-    rec = {"B": B, "T": T, "E": E, "H": H, "d_k": dk, "rate": args.rate, "causal": args.causal}
+    rec = {"B": B, "T": T, "E": E, "H": H, "d_k": dk, "rate": args.rate, "causal": args.causal,
+           "kernels": "stream" if stream else "long" if T > ops.ATTN_SHORT_MAXT else "short"}
     for k, v in ms.items():
         rec[f"{k}_ms"] = round(statistics.median(v), 4)
         rec[f"{k}_ms_min"] = round(min(v), 4)
         rec[f"{k}_ms_max"] = round(max(v), 4)
     flops = 14.0 * B * H * (T * (T + 1) / 2 if args.causal else T * T) * dk
     rec["hip_fraction_of_f32_mfma_peak"] = round(flops / PEAK_F32_MFMA * 1e3 / rec["hip_ms"], 3)
+    if "long" in fns:
+        rec["stream_over_long"] = round(rec["hip_ms"] / rec["long_ms"], 3)
     if not args.no_torch:
         rec["eager_over_hip"] = round(rec["eager_ms"] / rec["hip_ms"], 2)
         if args.rate == 0.0:                     # (eager's dropout draws another mask)

@@ -64,8 +64,9 @@ METRICS_K = (10, 20, 50)
 # ---------------------------------------------------- fused HIP encoder ops
 # On GPU the attention core (scores, key-padding mask, softmax, dropout, P.V)
 # and every LayerNorm run as hand-written kernels (csrc/kernels/attention.hip,
-# attention_long.hip above T = 64, layernorm.hip); on CPU the same modules run
-# the torch reference ops. Supported on the GPU: max_len <= 512, embed_dim in
+# attention_long.hip above T = 64, attention_stream.hip above T = 512,
+# layernorm.hip); on CPU the same modules run
+# the torch reference ops. Supported on the GPU: max_len <= 4096, embed_dim in
 # {16, 32, 64, 128, 256}, embed_dim / heads in {4, 8, 16, 32, 64},
 # max_len * embed_dim <= 32768 (check_gpu_shape).
 USE_FUSED = True
@@ -78,13 +79,13 @@ def check_gpu_shape(max_len: int, embed_dim: int, n_heads: int, causal: bool = F
     CPU path has no such limits). A causal model has no joint [T, E] row, so
     max_len * embed_dim is not limited there."""
     ok = (embed_dim in GPU_EMBED_DIMS and n_heads > 0 and embed_dim % n_heads == 0
-          and embed_dim // n_heads in ops.ATTN_DK and 0 < max_len <= ops.ATTN_LONG_MAXT
+          and embed_dim // n_heads in ops.ATTN_DK and 0 < max_len <= ops.ATTN_STREAM_MAXT
           and (causal or max_len * embed_dim <= GPU_MAX_ROW))
     if not ok:
         row = "" if causal else f" and max_len * embed_dim <= {GPU_MAX_ROW}"
         raise ValueError(
             f"Bert4Rec on the GPU supports embed_dim in {GPU_EMBED_DIMS}, d_k = embed_dim / "
-            f"heads in {ops.ATTN_DK}, max_len <= {ops.ATTN_LONG_MAXT}{row}; "
+            f"heads in {ops.ATTN_DK}, max_len <= {ops.ATTN_STREAM_MAXT}{row}; "
             f"got embed_dim = {embed_dim}, heads = {n_heads}, max_len = {max_len}")
 # whole transformer block in one fwd / one bwd kernel (encoder.hip); False
 # keeps the per-op path (fused attention core + LayerNorm kernels, torch GEMMs)
@@ -104,7 +105,15 @@ class _AttnCoreFn(torch.autograd.Function):
         qkv = qkv.contiguous()
         B, T, E3 = qkv.shape
         out = torch.empty(B, T, E3 // 3, dtype=qkv.dtype, device=qkv.device)
-        if T > ops.ATTN_SHORT_MAXT:
+        if T > ops.ATTN_LONG_MAXT:
+            # streaming kernels (T to 4096): as below, with D = dO . O from a
+            # pre-pass into the workspace delta, allocated next to lse
+            lse = torch.empty(B, H, T, dtype=torch.float32, device=qkv.device)
+            delta = torch.empty_like(lse)
+            ops.attention_stream_fwd(qkv, ids, H, rate, seed, step, PAD_ID, out, lse,
+                                     causal=causal)
+            ctx.save_for_backward(qkv, ids, step, out, lse, delta)
+        elif T > ops.ATTN_SHORT_MAXT:
             # tiled kernels: the backward recomputes P from the saved row
             # log-sum-exp and takes rowsum(P o dP) from dO . O
             lse = torch.empty(B, H, T, dtype=torch.float32, device=qkv.device)
@@ -121,7 +130,11 @@ class _AttnCoreFn(torch.autograd.Function):
         qkv, ids, step = ctx.saved_tensors[:3]
         H, rate, seed, causal = ctx.cfg
         dqkv = torch.empty_like(qkv)
-        if len(ctx.saved_tensors) > 3:
+        if len(ctx.saved_tensors) > 5:
+            out, lse, delta = ctx.saved_tensors[3:]
+            ops.attention_stream_bwd(qkv, ids, g.contiguous(), H, rate, seed, step, PAD_ID, dqkv,
+                                     out, lse, delta, causal=causal)
+        elif len(ctx.saved_tensors) > 3:
             out, lse = ctx.saved_tensors[3:]
             ops.attention_bwd(qkv, ids, g.contiguous(), H, rate, seed, step, PAD_ID, dqkv,
                               out=out, lse=lse, causal=causal)

@@ -1092,6 +1092,54 @@ def attention_bwd(qkv, ids, dout, H, rate, seed, step, pad_id, dqkv, out=None, l
         ref.attention_bwd(qkv, ids, dout, H, rate, seed, step, pad_id, dqkv, causal=causal)
 
 
+ATTN_STREAM_MAXT = 4096    # streaming kernels (LDS independent of T): attention_stream.hip
+
+
+def _attn_stream_check(qkv, H, named):
+    """Host-side argument checks of the streaming attention ops (CPU and GPU;
+    no kernel is launched on a failure). ``named``: (name, tensor, shape)."""
+    B, T = qkv.shape[0], qkv.shape[1]
+    dk = qkv.shape[2] // 3 // max(1, int(H))
+    if not ATTN_SHORT_MAXT < T <= ATTN_STREAM_MAXT or dk not in ATTN_DK:
+        raise ValueError(f"streaming attention supports {ATTN_SHORT_MAXT} < T <= "
+                         f"{ATTN_STREAM_MAXT} and d_k = E / H in {ATTN_DK}; got T = {T}, "
+                         f"d_k = {dk}")
+    for name, t, shape in named:
+        if t is None or t.dtype != torch.float32 or tuple(t.shape) != tuple(shape):
+            raise ValueError(f"streaming attention needs {name} as an fp32 tensor {list(shape)}")
+
+
+def attention_stream_fwd(qkv, ids, H, rate, seed, step, pad_id, out, lse, causal=False):
+    """attention_fwd for 64 < T <= 4096 on kernels whose LDS use and per-block
+    set-up do not depend on T. Writes ``out`` [B,T,E] and the row log-sum-exp
+    ``lse`` (fp32 [B,H,T], required). The dropout hash keys a row by
+    (b*H + h) * 512 + i for T <= 512 (attention_fwd's mask) and by
+    (b*H + h) * 4096 + i above. On CPU tensors: the reference (lse untouched)."""
+    B, T = qkv.shape[0], qkv.shape[1]
+    _attn_stream_check(qkv, H, (("out", out, (B, T, qkv.shape[2] // 3)), ("lse", lse, (B, H, T))))
+    if _gpu(qkv):
+        _native().attention_stream_fwd(qkv, ids, int(H), float(rate), int(seed), step,
+                                       int(pad_id), out, lse, bool(causal))
+    else:
+        ref.attention_fwd(qkv, ids, H, rate, seed, step, pad_id, out, causal=causal)
+
+
+def attention_stream_bwd(qkv, ids, dout, H, rate, seed, step, pad_id, dqkv, out, lse, delta,
+                         causal=False):
+    """dqkv of attention_stream_fwd from the forward's ``out`` and ``lse``.
+    ``delta`` (fp32 [B,H,T], required) is a workspace: a pre-pass writes
+    D_i = dO_i . O_i into it on the same stream before the backward kernel."""
+    B, T, E = qkv.shape[0], qkv.shape[1], qkv.shape[2] // 3
+    _attn_stream_check(qkv, H, (("out", out, (B, T, E)), ("lse", lse, (B, H, T)),
+                                ("delta", delta, (B, H, T)), ("dout", dout, (B, T, E)),
+                                ("dqkv", dqkv, (B, T, 3 * E))))
+    if _gpu(qkv):
+        _native().attention_stream_bwd(qkv, ids, dout, int(H), float(rate), int(seed), step,
+                                       int(pad_id), dqkv, out, lse, delta, bool(causal))
+    else:
+        ref.attention_bwd(qkv, ids, dout, H, rate, seed, step, pad_id, dqkv, causal=causal)
+
+
 LN_NARROW_MAXN = 1024      # wider rows (to 32768) take the one-workgroup-per-row path
 
 

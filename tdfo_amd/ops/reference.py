@@ -771,12 +771,13 @@ def _hash3(a, b, c):
 def attn_keep_scale(B: int, H: int, T: int, rate: float, seed: int, step: int, device):
     """[B, H, T, T] dropout multiplier (keep / (1 - rate) or 0) of the fused kernel.
     A row is keyed by (b*H + h) * stride + i: stride 64 for T <= 64
-    (attention.hip), 512 above (attention_long.hip; 64 would give row
-    (h, i >= 64) the mask of row (h + 1, i - 64))."""
+    (attention.hip), 512 for T <= 512 (attention_long.hip; 64 would give row
+    (h, i >= 64) the mask of row (h + 1, i - 64)) and 4096 above
+    (attention_stream.hip, for the same reason)."""
     if rate <= 0:
         return torch.ones(B, H, T, T, device=device)
     a = (seed ^ ((step * 0x632BE5AB) & _M32)) & _M32
-    stride = 64 if T <= 64 else 512
+    stride = 64 if T <= 64 else 512 if T <= 512 else 4096
     bh = torch.arange(B * H, dtype=torch.int64, device=device).view(B, H, 1, 1)
     i = torch.arange(T, dtype=torch.int64, device=device).view(1, 1, T, 1)
     j = torch.arange(T, dtype=torch.int64, device=device).view(1, 1, 1, T)
